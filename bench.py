@@ -1,9 +1,15 @@
 #!/usr/bin/env python
 """motions/sec of the MLD sampling hot path on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
       N > 1 without torchrun: bench.py re-launches itself as N ranks (python -m torch.distributed.run, 127.0.0.1);
       under torchrun (RANK / WORLD_SIZE set) it is one of the N ranks.
+
+A plain run measures the headline only: set-up, W warm-up steps, ONE timed region of exactly K steps, the result line.  --full adds
+every other measurement below (single-batch and pipelined figures, rocprofv3 rooflines, requests-per-call sweep, CPU baseline, parity,
+other arithmetic modes, length mix, configs 4 / 5, CLIP tower) and repeats the timed region --repeats times (default 5, median reported).
+--dump-outputs DIR writes what the last timed step returned to its caller (latents and joints of that bs-64 request) as float32 .npy files;
+the inputs are seeded, so two builds can be compared output for output.
 
 One "step" = one pass of the hot path over one batch: 50-step DDIM latent sampling with classifier-free guidance ->
 motion-VAE decode -> (T,22,3) joints for B=64 synthetic HumanML3D-shaped prompts (config_mld_humanml3d.yaml, T=196),
@@ -12,7 +18,8 @@ independent bs-64 requests that are all available at t = 0; the serving entry (m
 them (default 32 = 2 048 motions) per call: ONE persistent launch runs the whole reverse loop of the call (a workgroup per 8
 motions, kernels/loop_fused.hpp), then one decode.  Calls are issued one after another on ONE stream: no calls in flight, no
 stream / hardware-queue placement to get right (round 2's headline needed both).  The timed region (exactly K steps between
-barrier + synchronize pairs) is repeated --repeats times; `value` is the median repetition, min / max are carried.
+barrier + synchronize pairs) is repeated --repeats times; `value` is the median repetition, min / max are carried.  A warm-up
+step is one untimed bs-64 request in the timed region's call shapes; every call shape is warmed (its graph captured) at least once.
 `single_batch` / `value_single_batch` is the same K steps issued strictly one bs-64 batch after another (the configuration
 BASELINE.json's metric names literally; since round 5 the reverse loop of such a call is ONE launch of workgroup clusters,
 kernels/loop_cluster.hpp), with its own roofline from a second rocprofv3 child.  Ranks are pure data parallel: weights are broadcast once
@@ -397,7 +404,7 @@ def bench_novae(local, dev, full, streams, B=64, T=196):
     """BASELINE config 4 shape (config_novae_humanml3d.yaml: raw-motion diffusion, trans_dec denoiser d=512, bs=64, T=196,
     DDPM).  The headline mode (f16x3) always runs the sampler's real 1000 steps (~5 s per pair of batches); the other
     two modes run 100 DDPM steps per batch (the same per-step work; their `value` is the EXTRAPOLATED 1000-step rate and says so)
-    unless --full.  Per arithmetic mode, `nfl` batches in flight on
+    unless --novae-full-length.  Per arithmetic mode, `nfl` batches in flight on
     one handle (a workspace and a stream each)."""
     nfl = len(streams)
     steps = 1000 if full else 100
@@ -596,6 +603,21 @@ def profile_child(a):
     torch.cuda.synchronize()
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: {name: array} -> dirname/<name>.npy in float32, refused above DUMP_LIMIT_BYTES in all."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), v)
+    return total
+
+
 def spread(ts):
     ts = sorted(ts)
     return {"median": ts[len(ts) // 2], "min": ts[0], "max": ts[-1], "n": len(ts)}
@@ -645,6 +667,7 @@ def emit(out):
                                                                                 "value_single_batch"))})
     line["other_workloads"] = ow
     line["distributed"] = pick(out.get("distributed") or {}, ("backend", "world_size", "distinct_devices", "data_path_collectives"))
+    line = {k: v for k, v in line.items() if v != {} and v != []}        # (a plain run measures the headline only: no rooflines, baselines or other workloads)
     line["evidence"] = {"file": path, "bytes": len(blob), "note": "every table of this run (kernels, decoder_roofline, sweeps, alt modes, other workloads in full): the file, and the EVIDENCE line on stderr"}
     text = json.dumps(line)
     if len(text) > 8000:                       # never: but the contract is one parseable line the driver's tail keeps whole
@@ -663,9 +686,13 @@ def main():
                     help="arithmetic mode of the headline (see the module docstring); the others are reported as alt_modes")
     ap.add_argument("--coalesce", type=int, default=int(os.environ.get("MLD_BENCH_COALESCE", "32")),
                     help="bs-64 requests per engine call (mldhip_sample_many), at most 32; 1 = one call per request")
-    ap.add_argument("--repeats", type=int, default=5, help="repetitions of the K-step timed region (median reported, min / max carried)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="repetitions of the K-step timed region (median reported, min / max carried); default 1, 5 with --full")
     ap.add_argument("--eager", action="store_true", help="disable hipGraph replay (debug)")
-    ap.add_argument("--full", action="store_true", help="run the config-4 leg at its real length (1000 DDPM steps; ~1 min)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement (single-batch / pipelined figures, rooflines, sweep, CPU baseline, parity, other modes and workloads)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs (latents, joints) to DIR/<name>.npy, float32")
+    ap.add_argument("--novae-full-length", action="store_true", help="with --full: run the config-4 leg at its real length in every mode (1000 DDPM steps; ~1 min)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-rocprof", action="store_true", help="skip the rocprofv3 children (rooflines fall back to HIP events)")
     ap.add_argument("--no-alt", action="store_true", help="skip the alternate arithmetic modes and serving shapes")
@@ -676,6 +703,8 @@ def main():
     a = ap.parse_args()
     if a.profile_child:
         return profile_child(a)
+    if a.repeats is None:
+        a.repeats = 5 if a.full else 1
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher -- one rank per GPU under torch.distributed.run, same flags
@@ -719,12 +748,15 @@ def main():
         ranks_seen = [None] * world
         dist.all_gather_object(ranks_seen, ident)
     stream = torch.cuda.current_stream()
-    reqs_all = make_requests(dev, MAXC, rank, with_lat=True)
+    reqs_all = make_requests(dev, MAXC if a.full else coalesce, rank, with_lat=True)     # (seeded per slot: the first `coalesce` are the same either way)
     reqs = reqs_all[:coalesce]
     calls = [coalesce] * (K // coalesce) + ([K % coalesce] if K % coalesce else [])     # requests per call of one timed region: exactly K steps
+    warm = sorted(set(calls), reverse=True)      # warm-up: every call shape of the timed region once (its graph is captured), then W steps in all at least
+    while sum(warm) < a.warmup:
+        warm.append(calls[0])
 
-    def issue(e_, lengths=None):
-        for n in calls:
+    def issue(e_, lengths=None, shape=None):
+        for n in shape or calls:
             if n == 1:
                 r = reqs[0]
                 e_.sample(r["text_emb"], r["init_latents"], lengths[0] if lengths else r["lengths"], r["latents_out"], None, r["joints_out"], stream.cuda_stream)
@@ -760,50 +792,54 @@ def main():
         return dt, per_rank
 
     torch.cuda.synchronize()                     # inputs were uploaded on the default stream
-    for _ in range(max(a.warmup, 1)):            # W untimed rounds of the K steps: every call shape of the timed region is captured
-        issue(eng)
+    issue(eng, shape=warm)
     launches_headline = eng.launch_counts()      # [reverse loop, decode, joints] launches of the last (headline-shaped) call
     numeric0 = eng.numeric_status()              # what finalize's range probe decided (mldhip.h "Range contract")
-    issue_single(eng, 2)
-    launches_single = eng.launch_counts()        # ... of a single bs-64 call
+    if a.full:
+        issue_single(eng, 2)
+        launches_single = eng.launch_counts()    # ... of a single bs-64 call
     reps = [timed(lambda: issue(eng)) for _ in range(max(1, a.repeats))]
     order = sorted(range(len(reps)), key=lambda i: reps[i][0])
     dt, per_rank_s = reps[order[len(order) // 2]]            # the median repetition IS the reported K-step region
     ms_per_step = dt / K * 1e3
     value = world * BATCH * K / dt
-    K1 = min(K, 16)
-    reps1 = [timed(lambda: issue_single(eng, K1))[0] / K1 for _ in range(max(1, a.repeats))]     # strictly one bs-64 batch after another
-    ms1 = spread(reps1)
-    # ---- bs-64 requests back to back with the two halves of consecutive requests overlapped ("many_pipeline": decode of request k on the engine's side stream beside the
-    #      cluster launch of request k + 1; every request bit-identical to its serial mldhip_sample call -- tests/test_gpu_parity.py).  K steps per timed region, as above.
-    pipe = None
-    try:
-        engp = make_engine(local, weights, a.precision, max_batch=BATCH, nfl=2, graph=not a.eager)
-        engp.set_option("many_pipeline", 1)
-        KP = min(K, 32)
-        pcalls = [KP] * (K // KP) + ([K % KP] if K % KP else [])
+    if a.dump_outputs and rank == 0:
+        last = reqs[calls[-1] - 1]               # the last timed step = the last request of the last call (its buffers are not touched again before this)
+        dump_outputs(a.dump_outputs, {"latents": last["latents_out"].cpu().numpy(), "joints": last["joints_out"].cpu().numpy()})
+    if a.full:                                   # the single-batch and pipelined figures
+        K1 = min(K, 16)
+        reps1 = [timed(lambda: issue_single(eng, K1))[0] / K1 for _ in range(max(1, a.repeats))]     # strictly one bs-64 batch after another
+        ms1 = spread(reps1)
+        # ---- bs-64 requests back to back with the two halves of consecutive requests overlapped ("many_pipeline": decode of request k on the engine's side stream beside the
+        #      cluster launch of request k + 1; every request bit-identical to its serial mldhip_sample call -- tests/test_gpu_parity.py).  K steps per timed region, as above.
+        pipe = None
+        try:
+            engp = make_engine(local, weights, a.precision, max_batch=BATCH, nfl=2, graph=not a.eager)
+            engp.set_option("many_pipeline", 1)
+            KP = min(K, 32)
+            pcalls = [KP] * (K // KP) + ([K % KP] if K % KP else [])
 
-        def issue_pipe():
-            for n in pcalls:
-                if n == 1:
-                    r = reqs_all[0]
-                    engp.sample(r["text_emb"], r["init_latents"], r["lengths"], r["latents_out"], None, r["joints_out"], stream.cuda_stream)
-                else:
-                    engp.sample_many(reqs_all[:n], stream.cuda_stream)
-        issue_pipe(); issue_pipe()
-        repsp = [timed(issue_pipe)[0] / K for _ in range(max(1, a.repeats))]
-        msp = spread(repsp)
-        nsp = engp.numeric_status()
-        pipe = {"value": round(world * BATCH / msp["median"], 2), "unit": "motions/s", "ms_per_request": {k: (round(v * 1e3, 4) if k != "n" else v) for k, v in msp.items()},
-                "requests_per_call": KP, "numeric": {k: nsp[k] for k in ("nonfinite_values", "cluster_loop")},
-                "shape": "mldhip_sample_many with option many_pipeline = 1: %d bs-64 requests per call, one after the other on the single-request path (cluster loop), decode of "
-                         "request k on the engine's low-priority side stream beside the reverse loop of request k + 1; two workspaces alternate; the caller's stream is ordered "
-                         "behind every decode at the end of the call" % KP}
-        engp.close()
-    except Exception as ex_:      # never fail the single-process bench line for the secondary leg
-        if dist:                  # ... but under torch.distributed a rank that skipped its barriers would hang the others: fail loudly instead
-            raise
-        pipe = {"value": None, "error": repr(ex_)[:300]}
+            def issue_pipe():
+                for n in pcalls:
+                    if n == 1:
+                        r = reqs_all[0]
+                        engp.sample(r["text_emb"], r["init_latents"], r["lengths"], r["latents_out"], None, r["joints_out"], stream.cuda_stream)
+                    else:
+                        engp.sample_many(reqs_all[:n], stream.cuda_stream)
+            issue_pipe(); issue_pipe()
+            repsp = [timed(issue_pipe)[0] / K for _ in range(max(1, a.repeats))]
+            msp = spread(repsp)
+            nsp = engp.numeric_status()
+            pipe = {"value": round(world * BATCH / msp["median"], 2), "unit": "motions/s", "ms_per_request": {k: (round(v * 1e3, 4) if k != "n" else v) for k, v in msp.items()},
+                    "requests_per_call": KP, "numeric": {k: nsp[k] for k in ("nonfinite_values", "cluster_loop")},
+                    "shape": "mldhip_sample_many with option many_pipeline = 1: %d bs-64 requests per call, one after the other on the single-request path (cluster loop), decode of "
+                             "request k on the engine's low-priority side stream beside the reverse loop of request k + 1; two workspaces alternate; the caller's stream is ordered "
+                             "behind every decode at the end of the call" % KP}
+            engp.close()
+        except Exception as ex_:      # never fail the single-process bench line for the secondary leg
+            if dist:                  # ... but under torch.distributed a rank that skipped its barriers would hang the others: fail loudly instead
+                raise
+            pipe = {"value": None, "error": repr(ex_)[:300]}
     gf_total, gf_den, gf_dec = algorithmic_gflop(BATCH, FRAMES)
     tf_job = gf_total / 1e3 / (ms_per_step * 1e-3)
     PB = BATCH * coalesce
@@ -821,18 +857,20 @@ def main():
                    "requests_per_call": coalesce, "calls_per_timed_region": len(calls), "in_flight": 1, "global_batch": PB * world, "batch_per_request": BATCH,
                    "parallelism": f"dp{world}", "graph": not a.eager, "precision": a.precision,
                    "weights": "synthetic (seeded numpy), one broadcast of %.1f MB" % (weight_bytes / 1e6),
-                   "launches_per_call": launches_headline,
-                   # the configuration BASELINE.json's metric is quoted on, inside `config` so that a parser that keeps only the contract's keys keeps it (VERDICT r5 item 6)
-                   "value_single_batch": round(world * BATCH / ms1["median"], 2), "ms_single_batch": round(ms1["median"] * 1e3, 4),
-                   "value_bs64_pipelined": pipe.get("value") if pipe else None,
-                   "ms_per_request_bs64_pipelined": (pipe.get("ms_per_request") or {}).get("median") if pipe else None,
-                   "single_batch_note": "value_single_batch: ONE bs-64 mldhip_sample call at a time, strictly serial (the metric's literal configuration); value_bs64_pipelined: the same "
-                                        "bs-64 requests back to back with decode(k) beside loop(k + 1) (many_pipeline); value: the serving shape, requests_per_call requests as one chain"},
+                   "launches_per_call": launches_headline},
         "whole_job": {"algorithmic_gflop_per_batch": round(gf_total, 1), "denoise_gflop_per_step": round(gf_den, 3), "decode_gflop": round(gf_dec, 1),
                       "achieved_tflops": round(tf_job, 2), "frac_of_fp32_mfma_peak": round(tf_job / FP32_MFMA_PEAK_TF, 4),
                       "frac_of_mode_peak": round(tf_job / PEAK_TF[a.precision], 4), "mode_peak_tflops": round(PEAK_TF[a.precision], 1),
                       "note": "per GPU; mode peak = the MFMA roof of the headline arithmetic (f16x3: dense f16 peak / 3 products)"},
     }
+    if a.full:
+        out["config"].update({
+                   # the configuration BASELINE.json's metric is quoted on, inside `config` so that a parser that keeps only the contract's keys keeps it (VERDICT r5 item 6)
+                   "value_single_batch": round(world * BATCH / ms1["median"], 2), "ms_single_batch": round(ms1["median"] * 1e3, 4),
+                   "value_bs64_pipelined": pipe.get("value") if pipe else None,
+                   "ms_per_request_bs64_pipelined": (pipe.get("ms_per_request") or {}).get("median") if pipe else None,
+                   "single_batch_note": "value_single_batch: ONE bs-64 mldhip_sample call at a time, strictly serial (the metric's literal configuration); value_bs64_pipelined: the same "
+                                        "bs-64 requests back to back with decode(k) beside loop(k + 1) (many_pipeline); value: the serving shape, requests_per_call requests as one chain"})
     ns = eng.numeric_status()
     out["numeric"] = {"range_probe": numeric0, "nonfinite_values_in_timed_calls": ns["nonfinite_values"],
                       "note": "F16X3 range contract: probe at finalize (split-f16 vs exact-fp32 kernels of the same handle), fp32 fallback per stage above MLDHIP_PROBE_TOL = %g, "
@@ -844,7 +882,7 @@ def main():
                                                "note": "one packed broadcast from rank 0 (includes host->device staging on rank 0)"},
                           "per_rank_motions_per_s": {"min": round(min(per_rank_v), 2), "max": round(max(per_rank_v), 2)},
                           "data_path_collectives": 0}
-    if rank == 0:
+    if rank == 0 and a.full:
         solo = world == 1 and not a.eager
         # ---- headline call shape under rocprofv3 (child process, same call shape, one call at a time): per-kernel table + the dominant kernel
         stats, where = (None, "disabled") if (a.no_rocprof or dist is not None or a.eager) else rocprof_child_stats(a.precision, coalesce)
@@ -1116,7 +1154,7 @@ def main():
             if not a.no_a2m:
                 out["other_workloads"].append(bench_a2m(local, dev, 2, 8, s2))
             if not a.no_novae:
-                out["other_workloads"].append(bench_novae(local, dev, a.full, s2))
+                out["other_workloads"].append(bench_novae(local, dev, a.novae_full_length, s2))
         if world == 1 and not a.no_clip:
             try:
                 te = bench_text_encoder(dev)
@@ -1125,6 +1163,7 @@ def main():
                 out["text_encoder"] = te
             except Exception as ex_:  # transformers missing / API drift: report, never fail the bench
                 out["text_encoder"] = {"error": repr(ex_)[:200]}
+    if rank == 0:
         emit(out)
     if dist:
         dist.barrier()

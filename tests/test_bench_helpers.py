@@ -63,3 +63,15 @@ def test_decoder_roofline_from_the_committed_rocprof_summary(bench):
     assert abs(r["traffic"] - pmc["kernels"]["den_loop"]["traffic_bytes_per_launch"]) < 1e-3 * r["traffic"] and 0.3 < r["frac"] < 0.6
     assert abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-3 and abs(r["achieved"] - r["gflop_per_launch"] / r["avg_us_rocprof_dispatch"] * 1e3) < 0.5      # frac = the rocprofv3 figure
     assert abs(r["achieved_hip_events"] - r["gflop_per_launch"] / r["avg_us_hip_events_loop_only_call"] * 1e3) < 0.5 and abs(r["frac_hip_events"] - r["achieved_hip_events"] / r["peak"]) < 1e-3
+
+
+def test_dump_outputs_writes_float32_npy_and_refuses_more_than_64_mb(bench, tmp_path):
+    import numpy as np
+    lat, joints = np.arange(12, dtype=np.float64).reshape(2, 1, 6), np.linspace(-1, 1, 2 * 5 * 22 * 3).reshape(2, 5, 22, 3)
+    n = bench.dump_outputs(str(tmp_path / "out"), {"latents": lat, "joints": joints})
+    got = {k: np.load(str(tmp_path / "out" / (k + ".npy"))) for k in ("latents", "joints")}
+    assert n == (lat.size + joints.size) * 4 and all(v.dtype == np.float32 for v in got.values())
+    assert np.array_equal(got["latents"], lat.astype(np.float32)) and np.array_equal(got["joints"], joints.astype(np.float32))
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "big"), {"joints": np.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1, np.float32)})
+    assert not os.path.exists(str(tmp_path / "big"))

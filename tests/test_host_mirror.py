@@ -22,7 +22,11 @@ from oracle import mld_oracle as O
 # the simulator engines of this file run 3-layer skip stacks (tests/simlib.py): the YAML's layer counts are overridden to match
 TEXT_OVERRIDES = {"model.denoiser.params.num_layers": simlib.SIM_LAYERS, "model.motion_vae.params.num_layers": simlib.SIM_LAYERS}
 
-REF = "/root/reference"
+
+
+def reference_yaml(golden_dir, rel):
+    """The reference project's YAML at `rel`, as far as these tests read it (tests/golden/reference_yaml.json, oracle/make_golden_reference_yaml.py)."""
+    return json.load(open(os.path.join(golden_dir, "reference_yaml.json")))[rel]
 
 
 # ------------------------------------------------------------------------------------------ config
@@ -43,19 +47,18 @@ def test_config_merge_order_and_interpolation():
     assert over.model.denoiser.params.guidance_scale == 3.0                                   # interpolation sees override
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present")
-def test_hot_path_params_equal_the_reference_yamls():
+def test_hot_path_params_equal_the_reference_yamls(golden_dir):
     """Same `params:` blocks as configs/modules/*.yaml and same experiment keys (only targets differ)."""
     import yaml
     mine = C.load_config()
     for part, fn in (("denoiser", "denoiser.yaml"), ("motion_vae", "motion_vae.yaml"), ("scheduler", "scheduler.yaml")):
-        ref = yaml.safe_load(open(os.path.join(REF, "configs", "modules", fn)))[part]
+        ref = reference_yaml(golden_dir, "configs/modules/" + fn)[part]
         got = yaml.safe_load(open(os.path.join(C.CONFIG_DIR, "modules_hip", fn)))[part]
         assert ref["params"] == got["params"], part
         for k in ("num_inference_timesteps", "eta"):
             if k in ref:
                 assert ref[k] == got[k]
-    ref_exp = yaml.safe_load(open(os.path.join(REF, "configs", "config_mld_humanml3d.yaml")))
+    ref_exp = reference_yaml(golden_dir, "configs/config_mld_humanml3d.yaml")
     for k in ("latent_dim", "ff_size", "num_layers", "num_head", "guidance_scale", "guidance_uncondp", "condition", "vae"):
         assert ref_exp["model"][k] == mine.model[k], k
     assert ref_exp["TRAIN"]["ABLATION"] == {k: mine.TRAIN.ABLATION[k] for k in ref_exp["TRAIN"]["ABLATION"]}
@@ -210,20 +213,18 @@ def test_mld_forward_fused_and_modular_agree_with_oracle(sim_key):
 A2M_CFG = os.path.join(C.CONFIG_DIR, "config_mld_humanact12.yaml")
 
 
-def test_action_config_and_reference_yaml_parity():
+def test_action_config_and_reference_yaml_parity(golden_dir):
     cfg = C.load_config(A2M_CFG)
     assert cfg.model.condition == "action" and cfg.model.denoiser.target == "mld_hip.denoiser.HipMldDenoiser"
     assert cfg.model.denoiser.params.num_layers == 15 and cfg.model.denoiser.params.nclasses == 12
     assert cfg.model.motion_vae.target == "mld_hip.vae.HipActorVae" and cfg.model.motion_vae.params.num_layers == 6
     assert cfg.model.motion_vae.params.nfeats == 150
-    if not os.path.isdir(REF):
-        pytest.skip("reference tree not present")
     import yaml
     for part, fn in (("denoiser", "denoiser.yaml"), ("motion_vae", "motion_vae.yaml"), ("scheduler", "scheduler.yaml")):
-        ref = yaml.safe_load(open(os.path.join(REF, "configs", "modules_humanact12", fn)))[part]
+        ref = reference_yaml(golden_dir, "configs/modules_humanact12/" + fn)[part]
         got = yaml.safe_load(open(os.path.join(C.CONFIG_DIR, "modules_hip_humanact12", fn)))[part]
         assert ref["params"] == got["params"], part
-    ref_exp = yaml.safe_load(open(os.path.join(REF, "configs", "config_mld_humanact12.yaml")))
+    ref_exp = reference_yaml(golden_dir, "configs/config_mld_humanact12.yaml")
     for k in ("latent_dim", "ff_size", "num_layers", "num_head", "guidance_scale", "guidance_uncondp", "condition", "vae"):
         assert ref_exp["model"][k] == cfg.model[k], k
     assert ref_exp["TRAIN"]["ABLATION"] == {k: cfg.TRAIN.ABLATION[k] for k in ref_exp["TRAIN"]["ABLATION"]}
@@ -296,16 +297,14 @@ def test_novae_config_and_reference_yaml_parity(golden_dir):
     den = C.instantiate_from_config(cfg.model.denoiser)
     keys = json.load(open(os.path.join(golden_dir, "state_dict_keys.json")))
     assert {k: list(v.shape) for k, v in den.state_dict().items()} == keys["denoiser_novae"]
-    if not os.path.isdir(REF):
-        pytest.skip("reference tree not present")
     import yaml
     for part, fn in (("denoiser", "denoiser.yaml"), ("scheduler", "scheduler.yaml")):
-        ref = yaml.safe_load(open(os.path.join(REF, "configs", "modules_novae", fn)))[part]
+        ref = reference_yaml(golden_dir, "configs/modules_novae/" + fn)[part]
         got = yaml.safe_load(open(os.path.join(C.CONFIG_DIR, "modules_hip_novae", fn)))[part]
         assert ref["params"] == got["params"], part
         if part == "scheduler":
             assert ref["num_inference_timesteps"] == got["num_inference_timesteps"]
-    ref_exp = yaml.safe_load(open(os.path.join(REF, "configs", "config_novae_humanml3d.yaml")))
+    ref_exp = reference_yaml(golden_dir, "configs/config_novae_humanml3d.yaml")
     for k in ("latent_dim", "ff_size", "num_layers", "num_head", "guidance_scale", "guidance_uncondp", "condition", "vae", "vae_type"):
         assert ref_exp["model"][k] == cfg.model[k], k
 
