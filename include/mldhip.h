@@ -34,7 +34,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define MLDHIP_ABI_VERSION 5
+#define MLDHIP_ABI_VERSION 6
 
 enum {
   MLDHIP_OK = 0,
@@ -110,6 +110,11 @@ typedef struct mldhip_config {
   int32_t max_in_flight;        /* 1..8 activation workspaces sharing the weights.  Consecutive calls rotate through them, so
                                  * calls issued on DIFFERENT streams overlap on the GPU (a workspace is reused only after the
                                  * new call's stream has waited for its previous user).  1 = calls serialise as before. */
+  /* ---- ABI 6: stochastic DDIM (configs/modules/scheduler.yaml `eta`, passed to DDIMScheduler.step at mld.py:316-320,345-346) */
+  float eta;                    /* 0 (default) .. 1: sigma_t = eta * sqrt((1 - ab_p) / (1 - ab_t) * (1 - ab_t / ab_p)), fresh N(0,1) noise every step
+                                 * (the "Noise contract" below).  Read only when struct_size covers it (an ABI-5 caller's smaller struct means 0).
+                                 * mldhip_create refuses eta < 0, eta > 1, NaN, and eta != 0 with MLDHIP_SCHED_DDPM.  A handle with eta > 0 samples
+                                 * through mldhip_sample_many_seeded only: mldhip_sample / _action / _many fail with MLDHIP_ESTATE. */
 } mldhip_config;
 
 enum { MLDHIP_COND_TEXT = 0, MLDHIP_COND_ACTION = 1 };
@@ -201,7 +206,9 @@ int mldhip_finalize_weights(mldhip_handle* h, void* stream);
  *   "range_probe"     F16X3 mode: 1 (default) = mldhip_finalize_weights runs the range probe of the "Range contract" below, 0 = skips it
  *                     (the split kernels are used unconditionally), 2 = as 1, and the first text-conditioned mldhip_sample after finalize
  *                     repeats the reverse-loop part on the first 8 motions of ITS batch (the caller's embeddings and start noise) before
- *                     it samples: the verdict then covers a real prompt batch, not only the seeded one.  Setting it un-finalizes the handle
+ *                     it samples: the verdict then covers a real prompt batch, not only the seeded one.  Setting it un-finalizes the handle.
+ *                     The probe is deterministic on every handle, eta > 0 ones included: it runs the eta = 0 step (it measures the
+ *                     arithmetic of the kernels, not sampling)
  *   "ffn_strip"       F16X3 mode, decoder / encoder layers: strip height of the register-direct kernels (kernels/ffn_strip.hpp,
  *                     kernels/gemm_strip_x3.hpp): 1 (default) = by launch size -- more than 512 strips of 64 rows: 96-row strips for the
  *                     GEMMs, 48-row strips at two workgroups per CU for the feed-forward block; else 64 rows (one bs-64 request: 196
@@ -337,6 +344,28 @@ typedef struct mldhip_request {
 } mldhip_request;
 int mldhip_sample_many(mldhip_handle* h, const mldhip_request* reqs, int32_t nreq, void* stream);
 
+/* Stochastic DDIM (ABI 6).  Noise contract -- one definition for every reverse-loop path of the latent models:
+ *   inside one request, motion m (0-based) and latent element e (flat over latent_size x latent_dim, latent_elems of them) draw
+ *   at scheduler step i (0-based, in loop order)  z = element (first_index + m) * latent_elems + e  of the stream
+ *   mldhip_philox_normal(seed, step_index = i).
+ * A motion's noise is therefore a function of (seed, first_index + m, i) alone: not of the loop family or launch that serves it,
+ * its position in a coalesced chain, or how a data-parallel run sharded the prompts (pass each shard's global start index as
+ * first_index).  The step is diffusers' DDIMScheduler.step(eta) with the CFG-combined eps, z added at every step including the last:
+ *   x' = sqrt(ab_p) x0 + sqrt(1 - ab_p - sigma^2) eps + sigma z,   x0 = (x - sqrt(1 - ab_t) eps) / sqrt(ab_t).
+ * (A modular loop that draws z from torch's generator cannot reproduce these draws bit for bit; handed the Philox draws it agrees
+ * with the fused paths up to the mode's tolerance.) */
+typedef struct mldhip_noise_key {
+  uint64_t seed;
+  int64_t first_index;            /* global index of the request's motion 0 */
+} mldhip_noise_key;
+
+/* mldhip_sample_many with one noise key per request (keys[nreq]).  Serves text and action engines on the same path rules as
+ * mldhip_sample_many, "many_pipeline" 1 included (there every request is bit-identical to a one-request seeded call with the
+ * same key).  On an eta = 0 handle the keys are ignored and the results are bit-identical to mldhip_sample_many.  The keys are
+ * uploaded with every call: a new seed replays the already-captured graph. */
+int mldhip_sample_many_seeded(mldhip_handle* h, const mldhip_request* reqs, const mldhip_noise_key* keys, int32_t nreq,
+                              void* stream);
+
 /* Replaces: MldDenoiser.forward(sample, timestep, encoder_hidden_states)[0]
  * (mld/models/architectures/mld_denoiser.py:135-228).  sample [R,1,D], text [R,1,text_dim],
  * out [R,1,D]; any integer timestep in [0, num_train_timesteps). */
@@ -407,6 +436,12 @@ int mldhip_vae_encode(mldhip_handle* h, const float* feats_dev, const int32_t* l
  * mld.py:345-346).  n elements, in/out may alias. */
 int mldhip_ddim_step(mldhip_handle* h, const float* eps_dev, int32_t timestep, const float* sample_dev,
                      float* prev_sample_dev, int64_t n, void* stream);
+
+/* Replaces: DDIMScheduler.step(model_output, t, sample, eta=cfg.eta, variance_noise=z).prev_sample with the HANDLE's eta
+ * (ABI 6; DDIM handles only).  noise_dev [n] = the step's N(0,1) draw, or NULL: element i of mldhip_philox_normal(seed, step_index)
+ * (the Noise contract with first_index 0).  n elements, in/out may alias. */
+int mldhip_ddim_step_eta(mldhip_handle* h, const float* eps_dev, int32_t timestep, const float* sample_dev, const float* noise_dev,
+                         uint64_t seed, int32_t step_index, float* prev_sample_dev, int64_t n, void* stream);
 
 /* Replaces: HumanML3DDataModule.feats2joints (mld/data/HumanML3D.py:41-45 -> recover_from_ric,
  * mld/data/humanml/scripts/motion_process.py:415-432).  feats [B,T,nfeats] -> joints [B,T,njoints,3]. */

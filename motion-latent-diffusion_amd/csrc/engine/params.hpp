@@ -18,7 +18,7 @@ using E = mldhip_engine;
 void bind_context(E* e, int k) {
   WsContext& x = e->ctxs[k];
   for (auto& cv : e->carve) *cv.first = x.ws + cv.second;
-  e->lens_dev = x.lens; e->lens2_dev = x.lens2; e->labels_dev = x.labels;
+  e->lens_dev = x.lens; e->lens2_dev = x.lens2; e->labels_dev = x.labels; e->keys_dev = x.keys;
   e->cur_ctx = k;
 }
 
@@ -113,6 +113,8 @@ bool is_actor(const E* e) { return e->cfg.vae_arch == MLDHIP_VAE_ACTOR; }
 int time_width(const E* e) { return is_action(e) ? e->cfg.latent_dim : e->cfg.text_dim; }   // mld_denoiser.py:57-77
 bool is_novae(const E* e) { return e->cfg.vae_arch == MLDHIP_VAE_NONE; }
 bool is_ddpm(const E* e) { return e->cfg.scheduler_type == MLDHIP_SCHED_DDPM; }
+bool eta_on(const E* e) { return e->cfg.eta > 0.0f; }                       // stochastic DDIM handle (sampling needs noise keys)
+bool eta_live(const E* e) { return eta_on(e) && !e->noise_off; }            // ... and the reverse loop being issued draws noise
 int novae_kp(const E* e) { return (e->cfg.nfeats + 127) / 128 * 128; }   // feature width padded to 4 K chunks (263 -> 384)
 int vae_layers(const E* e) { return is_actor(e) ? (e->cfg.vae_num_layers > 0 ? e->cfg.vae_num_layers : e->cfg.num_layers) : e->cfg.num_layers; }
 std::string actor_layer(int i) { return "vae.decoder.seqTransDecoder.layers." + std::to_string(i); }
@@ -399,6 +401,18 @@ DdimCoef ddim_coef(const E* e, int t) {
   const float at = e->alphas_cumprod[t];
   const float ap = prev >= 0 ? e->alphas_cumprod[prev] : e->final_alpha_cumprod;
   return DdimCoef{sqrtf(at), sqrtf(1.0f - at), sqrtf(ap), sqrtf(1.0f - ap)};
+}
+
+// Stochastic DDIM (diffusers DDIMScheduler.step, eta > 0; float32): sigma = eta sqrt((1 - ab_p) / (1 - ab_t) (1 - ab_t / ab_p)),
+// the eps coefficient sqrt(1 - ab_p - sigma^2) (clamped at 0 against rounding; the DdimCoef of the step are unchanged).
+DdimEta ddim_eta(const E* e, int t) {
+  const auto& c = e->cfg;
+  const int prev = t - c.num_train_timesteps / c.num_inference_steps;
+  const float at = e->alphas_cumprod[t];
+  const float ap = prev >= 0 ? e->alphas_cumprod[prev] : e->final_alpha_cumprod;
+  const float var = (1.0f - ap) / (1.0f - at) * (1.0f - at / ap);
+  const float sigma = c.eta * sqrtf(var);
+  return DdimEta{sqrtf(fmaxf(1.0f - ap - sigma * sigma, 0.0f)), sigma};
 }
 
 // get_timestep_embedding(flip_sin_to_cos=True, freq_shift=0) (embeddings.py:245-285) for one t.

@@ -277,7 +277,7 @@ int build_loop_stream(Ctx& c) {
   }
   const size_t ips = items.size();
   for (int j = 0; j < 8; ++j) items.push_back(items[j]);      // the ring's look-ahead across the end of a step (loop_fused.hpp gload)
-  const size_t nit = items.size(), small_floats = (size_t)L * kLsLayer + (size_t)nb * 256 + 768, tail = (size_t)n * 4;
+  const size_t nit = items.size(), small_floats = (size_t)L * kLsLayer + (size_t)nb * 256 + 768, tail = (size_t)n * 6;
   if (e->loop_stream) { (void)hipFree(e->loop_stream); e->loop_stream = nullptr; }
   if (e->loop_small) { (void)hipFree(e->loop_small); e->loop_small = nullptr; }
   if (e->loop_stream_x3) { (void)hipFree(e->loop_stream_x3); e->loop_stream_x3 = nullptr; }
@@ -289,6 +289,7 @@ int build_loop_stream(Ctx& c) {
       hipMalloc((void**)&items_dev, nit * sizeof(LoopItem)) != hipSuccess)
     return e->fail(MLDHIP_EHIP, "hipMalloc(sample-major loop tables)");
   e->loop_ddim = e->loop_small + small_floats;
+  e->loop_eta = e->loop_ddim + (size_t)n * 4;
   hipError_t st = hipMemcpy(items_dev, items.data(), nit * sizeof(LoopItem), hipMemcpyHostToDevice);
   if (st == hipSuccess) {
     MLD_LAUNCH(pack_loop_stream_kernel<false>, dim3((unsigned)nit), dim3(512), 0, c.stream, (const float*)e->arena, (const LoopItem*)items_dev, e->loop_stream);
@@ -319,6 +320,12 @@ int build_loop_stream(Ctx& c) {
     coef[4 * s] = k.sqrt_at; coef[4 * s + 1] = k.sqrt_1mat; coef[4 * s + 2] = k.sqrt_ap; coef[4 * s + 3] = k.sqrt_1map;
   }
   if (st == hipSuccess) st = hipMemcpy(e->loop_ddim, coef.data(), coef.size() * sizeof(float), hipMemcpyHostToDevice);
+  std::vector<float> etab((size_t)n * 2);
+  for (int s = 0; s < n; ++s) {
+    const DdimEta k = ddim_eta(e, e->timesteps[s]);
+    etab[2 * s] = k.c_eps; etab[2 * s + 1] = k.sigma;
+  }
+  if (st == hipSuccess) st = hipMemcpy(e->loop_eta, etab.data(), etab.size() * sizeof(float), hipMemcpyHostToDevice);
   if (st != hipSuccess) return e->fail(MLDHIP_EHIP, "sample-major loop tables: %s", hipGetErrorString(st));
   e->loop_ips = (int)ips;
   return 0;
@@ -924,6 +931,11 @@ void launch_fused_loop(Ctx& c, const float* init_lat, int B, int n, float guidan
   a.lat = e->lat; a.skip = e->FS; a.ddim = e->loop_ddim; a.B = B; a.L = e->cfg.num_layers; a.n = n;
   a.guidance = guidance; a.init_sigma = 1.0f;
   const dim3 grid((B + 7) / 8);
+  if (eta_live(e)) {                    // stochastic DDIM: the step's second table row + the call's noise keys
+    a.eta = e->loop_eta; a.keys = e->keys_dev;
+    if (x3) MLD_LAUNCH((den_loop_kernel<true, kLoopEta>), grid, dim3(512), kLoopLdsBytes, c.stream, a);
+    else MLD_LAUNCH((den_loop_kernel<false, kLoopEta>), grid, dim3(512), kLoopLdsBytes, c.stream, a);
+  } else
 #if defined(MLDHIP_HOOKS)
   if (x3 && e->fused_dbg == 5) { a.trace = reinterpret_cast<unsigned long long*>(e->trace_buf); MLD_LAUNCH((den_loop_kernel<true, 5>), grid, dim3(512), kLoopLdsBytes, c.stream, a); }
   else
@@ -965,7 +977,16 @@ void launch_cluster_chunk(Ctx& c, const float* init_lat, int B, int s_base, int 
 #endif
   if (e->sample_part == 1) return;               // (the pipelined form captures what precedes the launch as a graph of its own)
   const dim3 grid((unsigned)(a.xslots * members * ((a.ncl + a.xslots - 1) / a.xslots)));
-  if (cg == 8) {
+  if (eta_live(e)) {                    // stochastic DDIM: the step's second table row + the call's noise keys
+    a.eta = e->loop_eta; a.keys = e->keys_dev;
+    if (cg == 8) {
+      if (e->cluster_wt) MLD_LAUNCH_CORESIDENT((den_cluster_eta_kernel<true, 8>), grid, dim3(512), kClLdsBytes, c.stream, a);
+      else MLD_LAUNCH_CORESIDENT((den_cluster_eta_kernel<false, 8>), grid, dim3(512), kClLdsBytes, c.stream, a);
+    } else {
+      if (e->cluster_wt) MLD_LAUNCH_CORESIDENT((den_cluster_eta_kernel<true, 4>), grid, dim3(512), kClLdsBytes, c.stream, a);
+      else MLD_LAUNCH_CORESIDENT((den_cluster_eta_kernel<false, 4>), grid, dim3(512), kClLdsBytes, c.stream, a);
+    }
+  } else if (cg == 8) {
     if (e->cluster_wt) MLD_LAUNCH_CORESIDENT((den_cluster_kernel<true, 8>), grid, dim3(512), kClLdsBytes, c.stream, a);
     else MLD_LAUNCH_CORESIDENT((den_cluster_kernel<false, 8>), grid, dim3(512), kClLdsBytes, c.stream, a);
   } else {
@@ -1025,6 +1046,11 @@ int enqueue_sample(E* e, hipStream_t stream, const float* text, const float* ini
     for (int s = 0; s < n && !c.rc; ++s) {
       denoiser_body(c, v);
       const float* t1n = (s + 1 < n) ? e->T1 + (size_t)(s + 1) * D : nullptr;
+      if (eta_live(e))
+        MLD_LAUNCH(den_final_step_eta_kernel, dim3(B), dim3(256), 0, stream, den_final_args(e, v), v.lat, v.X0,
+                   P(e, "denoiser.query_pos.pe"), t1n, B, guidance, ddim_coef(e, e->timesteps[s]), (const NoiseKey*)e->keys_dev, s,
+                   ddim_eta(e, e->timesteps[s]));
+      else
       MLD_LAUNCH(den_final_step_kernel, dim3(B), dim3(256), 0, stream, den_final_args(e, v), v.lat, v.X0,
                  P(e, "denoiser.query_pos.pe"), t1n, B, guidance, ddim_coef(e, e->timesteps[s]));
       count(c);

@@ -45,6 +45,8 @@ struct GraphKey {
 struct WsContext {
   float* ws = nullptr;
   int32_t *lens = nullptr, *lens2 = nullptr, *labels = nullptr;
+  NoiseKey* keys = nullptr;            // [max_batch] noise key per motion of the call (stochastic DDIM; uploaded with every call, like lens)
+  std::vector<NoiseKey> keys_host;     // stable host copy of what is uploaded to `keys`
   bool used = false;
   unsigned long long seed_host = 0;   // stable host copy of the Philox seed while it is uploaded to seed_slot
 #if !defined(MLDHIP_SIM)
@@ -76,6 +78,7 @@ struct mldhip_engine {
   float* loop_stream_x3 = nullptr;   // ... the same items as split-f16 images (the precision mode with split arithmetic)
   float* loop_small = nullptr;    // ... its biases / LayerNorm parameters, packed; then the DDIM coefficients [n][4]
   float* loop_ddim = nullptr;
+  float* loop_eta = nullptr;      // ... then the stochastic-DDIM table [n][2] (DdimEta: sqrt(1 - ab_p - sigma^2), sigma)
   int loop_ips = 0;               // weight items per reverse step (0: the variant is not built for this configuration)
   float* cl_stream = nullptr;     // cluster loop (kernels/loop_cluster.hpp): per column group and wave, the split-f16 fragments in consumption order
   unsigned cl_wave_off[96] = {0}; // ... float offset of (column group, wave)'s sequence: 32 words of the 4-group form, 64 of the 8-group form
@@ -115,6 +118,8 @@ struct mldhip_engine {
   unsigned next_ctx = 0;
   size_t ws_floats = 0;
   int32_t* lens_dev = nullptr;
+  NoiseKey* keys_dev = nullptr;   // the bound context's noise keys
+  bool noise_off = false;         // set while the range probe runs: it measures arithmetic on the eta = 0 kernels, also on an eta > 0 handle
   // denoiser
   float *X0, *Ha, *Hb, *H1, *S[8], *QKV, *AO, *FF, *lat, *T1, *temb0, *tmid, *text_bias, *t1_one, *temb0_one, *time_b2pe;
   // decode

@@ -58,6 +58,10 @@ __global__ __launch_bounds__(256) void split_bf16_weights_kernel(const float* __
 }
 
 struct DdimCoef { float sqrt_at, sqrt_1mat, sqrt_ap, sqrt_1map; };   // DDIM eta=0 coefficients of one step
+// Stochastic DDIM (eta > 0): the second per-step table, {sqrt(1 - ab_p - sigma^2), sigma}; x' = sqrt_ap x0 + c_eps eps + sigma z
+struct DdimEta { float c_eps, sigma; };
+// Noise key of one motion of a call (include/mldhip.h "Noise contract"): z of (step i, element e) is element index * 256 + e of Philox(seed, i)
+struct NoiseKey { unsigned long long seed; long long index; };
 
 // LayerNorm over rows of width 256: one wave per row, 4 rows per workgroup.
 __global__ __launch_bounds__(256) void layernorm_rows_kernel(const float* __restrict__ X, float* __restrict__ Y,

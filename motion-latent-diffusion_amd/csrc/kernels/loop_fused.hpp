@@ -72,7 +72,13 @@ struct LoopArgs {
   int B, L, n;
   float guidance, init_sigma;
   unsigned long long* trace = nullptr;   // DBG 5 (measurement build): [workgroup < 64][wave][8] shader cycles per phase, summed over steps and layers
+  const float* eta = nullptr;            // den_loop_kernel<X3, kLoopEta>: [n][2] DdimEta per step
+  const NoiseKey* keys = nullptr;        // ... [B] noise key per motion of the call
 };
+
+// den_loop_kernel<X3, kLoopEta>: the stochastic-DDIM form (eta > 0, include/mldhip.h "Noise contract") of the production loop.  It takes a value of
+// the variant parameter rather than a template parameter of its own, so the eta = 0 instantiations keep their names and their machine code.
+constexpr int kLoopEta = 6;
 
 #ifndef LF_EXP
 #define LF_EXP 0          // tools/loopbench experiments (measurement builds with WRONG results; 0 in the library): 1 / 4 = linear1 / linear2 re-use stale A
@@ -126,6 +132,7 @@ __global__ __launch_bounds__(512) void pack_loop_stream_kernel(const float* __re
 // DBG: 0 = the product build; 5 = the same arithmetic with phase counters (mldhip_set_option "fused_dbg" 5, tools/trace_loop.py).  1-4 are
 // measurement builds with WRONG results that only tools/loopbench instantiates -- they are not in libmldhip.so: 1 = the weight ring is
 // loaded once and never refreshed, 2 = the stream is loaded but not multiplied, 3 = identity instead of GELU, 4 = no feed-forward epilogue.
+// 6 (kLoopEta) = the product build with stochastic DDIM (eta > 0).
 // SWZ (split mode, always on): the 16-byte groups of an operand row are stored XOR-swizzled by the row -- physical word = logical word ^ 4 ((row >> 2) & 3),
 // i.e. group (g ^ (r >> 2)) of each 16-word half chunk.  The image's 8-byte row stores (put_row: sixteen rows 264 = 8 mod 32 words
 // apart per 16-lane group) hit each bank pair four times (ds_write_b64 is served per 16 contiguous lanes over 32 banks); swizzled,
@@ -133,6 +140,7 @@ __global__ __launch_bounds__(512) void pack_loop_stream_kernel(const float* __re
 // 2 r + (g ^ (r >> 2)) mod 16 is still a permutation inside each of the instruction's four lane groups; tests/test_lds_layout.py).
 template <bool X3, int DBG = 0>
 __global__ __launch_bounds__(512, 2) void den_loop_kernel(LoopArgs p) {
+  constexpr bool ETA = DBG == kLoopEta;   // stochastic DDIM: the step's second table row, sigma z added at the DDIM update (z drawn per (r < 8, cb) quad)
   constexpr int kLoopRing = LF_RING;      // items in flight per lane.  (r03: 8 spilled ring slots around the epilogues at the 256-register cap and lost, 33.1 vs
                                           // 29.3 ms; with the skip linears pinned -- pin_acc: 194 registers, no scratch -- 8 wins: 19.07 / 18.65 ms at 1 280 motions for
                                           // no pins + ring 4 / pins + ring 8, 25.25 / 24.99 ms at 2 048, profiles/r04_loop_experiments.json)
@@ -741,7 +749,7 @@ __global__ __launch_bounds__(512, 2) void den_loop_kernel(LoopArgs p) {
           __syncthreads();
         }
       } else {
-      // ================= behind the last layer: end of the step: encoder.norm on the latent token (mld_denoiser.py:206), CFG (mld.py:339-342), DDIM eta = 0
+      // ================= behind the last layer: end of the step: encoder.norm on the latent token (mld_denoiser.py:206), CFG (mld.py:339-342), DDIM (eta = 0, or + sigma z)
       {
         ln_part1(x, 1);
         __syncthreads();
@@ -757,12 +765,27 @@ __global__ __launch_bounds__(512, 2) void den_loop_kernel(LoopArgs p) {
             const F4 xt = ld4(lp);
             const float xtv[4] = {xt.x, xt.y, xt.z, xt.w};
             float nv[4];
+            if constexpr (ETA) {
+              // x' = sqrt_ap x0 + sqrt(1 - ab_p - sigma^2) eps + sigma z (rows of a last workgroup's missing motions hold no key: z = 0 there)
+              const float ce = p.eta[step * 2], sg = p.eta[step * 2 + 1];
+              float z[4] = {0.f, 0.f, 0.f, 0.f};
+              if (s0 + r < p.B) latent_noise4(p.keys[s0 + r], (unsigned)step, (cb * 128 + cq0) >> 2, z);
+#pragma unroll
+              for (int i = 0; i < 4; ++i) {
+                const float eu = x[cb][0][i];
+                const float eps = eu + p.guidance * (ec[i] - eu);
+                const float x0 = (xtv[i] - s1mat * eps) / sat;
+                nv[i] = sap * x0 + ce * eps;
+                nv[i] += sg * z[i];
+              }
+            } else {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
               const float eu = x[cb][0][i];
               const float eps = eu + p.guidance * (ec[i] - eu);
               const float x0 = (xtv[i] - s1mat * eps) / sat;
               nv[i] = sap * x0 + s1map * eps;
+            }
             }
             st4(lp, F4{nv[0], nv[1], nv[2], nv[3]});
           }

@@ -658,6 +658,11 @@ __device__ __forceinline__ void philox_normal4(unsigned long long seed, unsigned
   z[0] = r0 * cosf(t0); z[1] = r0 * sinf(t0); z[2] = r1 * cosf(t1); z[3] = r1 * sinf(t1);
 }
 
+// The four N(0,1) draws of latent elements 4 q .. 4 q + 3 of the motion keyed by k at scheduler step `step` (the latent paths are 256 wide: 64 quads per motion).
+__device__ __forceinline__ void latent_noise4(const NoiseKey& k, unsigned step, int q, float (&z)[4]) {
+  philox_normal4(k.seed, step, (unsigned long long)(k.index * 64 + q), z);
+}
+
 // out[n] = N(0,1) of (seed, step, element) -- exposed for tests / callers that want the engine's noise stream.
 __global__ __launch_bounds__(256) void philox_normal_kernel(float* __restrict__ out, long long n, unsigned long long seed, unsigned step) {
   const long long nq = (n + 3) / 4;

@@ -388,9 +388,12 @@ __device__ __forceinline__ float final_row_value(const FinalArgs& f, long long r
   return xc * rsqrtf(var + kLnEps) * f.gf[d] + f.bef[d];
 }
 
-__global__ __launch_bounds__(256) void den_final_step_kernel(FinalArgs f, float* __restrict__ lat, float* __restrict__ X0,
-                                                             const float* __restrict__ pe0, const float* __restrict__ t1_next,
-                                                             int B, float guidance, DdimCoef c) {
+// ETA (den_final_step_eta_kernel): x' = sqrt_ap x0 + k.c_eps eps + k.sigma z, z of (keys[b], step, d) -- every thread draws the Philox quad of its
+// element and keeps its own of the four (the quad's other lanes draw the same call: no exchange)
+template <bool ETA>
+__device__ __forceinline__ void den_final_step_body(const FinalArgs& f, float* __restrict__ lat, float* __restrict__ X0,
+                                                    const float* __restrict__ pe0, const float* __restrict__ t1_next,
+                                                    int B, float guidance, const DdimCoef& c, const NoiseKey* __restrict__ keys, int step, DdimEta k) {
   __shared__ float sh[4];
   const int b = blockIdx.x, d = threadIdx.x, R = 2 * B;
   const float eu = final_row_value(f, b, d, sh);
@@ -398,7 +401,17 @@ __global__ __launch_bounds__(256) void den_final_step_kernel(FinalArgs f, float*
   const float eps = eu + guidance * (ec - eu);
   const float x = lat[(long long)b * 256 + d];
   const float x0 = (x - c.sqrt_1mat * eps) / c.sqrt_at;
-  const float xn = c.sqrt_ap * x0 + c.sqrt_1map * eps;
+  float xn;
+  if constexpr (ETA) {
+    float z[4];
+    latent_noise4(keys[b], (unsigned)step, d >> 2, z);
+    const int j = d & 3;
+    const float zj = j == 0 ? z[0] : j == 1 ? z[1] : j == 2 ? z[2] : z[3];
+    xn = c.sqrt_ap * x0 + k.c_eps * eps;
+    xn += k.sigma * zj;
+  } else {
+    xn = c.sqrt_ap * x0 + c.sqrt_1map * eps;
+  }
   lat[(long long)b * 256 + d] = xn;
   const float tok = xn + pe0[d];
   X0[(long long)b * 256 + d] = tok;
@@ -408,6 +421,18 @@ __global__ __launch_bounds__(256) void den_final_step_kernel(FinalArgs f, float*
     X0[(long long)(R + b) * 256 + d] = tt;
     X0[(long long)(R + B + b) * 256 + d] = tt;
   }
+}
+
+__global__ __launch_bounds__(256) void den_final_step_kernel(FinalArgs f, float* __restrict__ lat, float* __restrict__ X0,
+                                                             const float* __restrict__ pe0, const float* __restrict__ t1_next,
+                                                             int B, float guidance, DdimCoef c) {
+  den_final_step_body<false>(f, lat, X0, pe0, t1_next, B, guidance, c, nullptr, 0, DdimEta{0.f, 0.f});
+}
+
+__global__ __launch_bounds__(256) void den_final_step_eta_kernel(FinalArgs f, float* __restrict__ lat, float* __restrict__ X0,
+                                                                 const float* __restrict__ pe0, const float* __restrict__ t1_next,
+                                                                 int B, float guidance, DdimCoef c, const NoiseKey* __restrict__ keys, int step, DdimEta k) {
+  den_final_step_body<true>(f, lat, X0, pe0, t1_next, B, guidance, c, keys, step, k);
 }
 
 // Stand-alone MldDenoiser.forward output: out[r] = LN_final(LN2(...)) for the R token-0 rows.  grid = R.

@@ -23,6 +23,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -159,7 +160,17 @@ const char* mldhip_last_error(mldhip_handle* h) { return h ? h->err.c_str() : g_
 int mldhip_create(const mldhip_config* cfg, int device, mldhip_handle** out) {
   auto bad = [&](const char* m) { g_last_error = m; return MLDHIP_EINVAL; };
   if (!cfg || !out) return bad("null argument");
-  if (cfg->struct_size != (int32_t)sizeof(mldhip_config)) return bad("mldhip_config.struct_size mismatch (ABI skew)");
+  // ABI 6 appended `eta`: a caller built against ABI 5 passes the smaller struct (eta is 0 then); the fields are read from a full-size copy
+  constexpr int32_t kCfgAbi5 = (int32_t)offsetof(mldhip_config, eta);
+  if (cfg->struct_size != (int32_t)sizeof(mldhip_config) && cfg->struct_size != kCfgAbi5) return bad("mldhip_config.struct_size mismatch (ABI skew)");
+  mldhip_config full;
+  std::memset(&full, 0, sizeof full);
+  std::memcpy(&full, cfg, (size_t)cfg->struct_size);
+  full.struct_size = (int32_t)sizeof(mldhip_config);
+  cfg = &full;
+  if (!(cfg->eta >= 0.0f && cfg->eta <= 1.0f)) return bad("eta must be in [0, 1] (DDIMScheduler.step; NaN refused)");
+  if (cfg->eta != 0.0f && cfg->scheduler_type != MLDHIP_SCHED_DDIM) return bad("eta != 0 needs the DDIM scheduler (DDPMScheduler.step has no eta)");
+  if (cfg->eta != 0.0f && (cfg->latent_size * cfg->latent_dim) % 4 != 0) return bad("eta != 0: latent_size x latent_dim must be a multiple of 4 (one Philox call = 4 draws)");
   const bool novae = cfg->vae_arch == MLDHIP_VAE_NONE;
   if (cfg->vae_arch != MLDHIP_VAE_MLD && cfg->vae_arch != MLDHIP_VAE_ACTOR && !novae) return bad("vae_arch must be mld, actor or none");
   if (cfg->denoiser_arch != MLDHIP_ARCH_TRANS_ENC && cfg->denoiser_arch != MLDHIP_ARCH_TRANS_DEC) return bad("denoiser_arch must be trans_enc or trans_dec");
@@ -276,7 +287,9 @@ int mldhip_create(const mldhip_config* cfg, int device, mldhip_handle** out) {
     if (hipMalloc((void**)&x.ws, off * sizeof(float)) != hipSuccess) { e->err = "hipMalloc(workspace) failed"; return fail_create(MLDHIP_EHIP); }
     if (hipMemset(x.ws, 0, off * sizeof(float)) != hipSuccess) { e->err = "hipMemset(workspace) failed"; return fail_create(MLDHIP_EHIP); }
     if (hipMalloc((void**)&x.lens, 2 * Bm * sizeof(int32_t)) != hipSuccess || hipMalloc((void**)&x.lens2, Bm * sizeof(int32_t)) != hipSuccess ||
-        hipMalloc((void**)&x.labels, 2 * Bm * sizeof(int32_t)) != hipSuccess) { e->err = "hipMalloc(lens) failed"; return fail_create(MLDHIP_EHIP); }
+        hipMalloc((void**)&x.labels, 2 * Bm * sizeof(int32_t)) != hipSuccess || hipMalloc((void**)&x.keys, Bm * sizeof(NoiseKey)) != hipSuccess ||
+        hipMemset(x.keys, 0, Bm * sizeof(NoiseKey)) != hipSuccess) { e->err = "hipMalloc(lens) failed"; return fail_create(MLDHIP_EHIP); }
+    x.keys_host.assign(Bm, NoiseKey{0ull, 0ll});
 #if !defined(MLDHIP_SIM)
     if (hipEventCreateWithFlags(&x.done, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&x.loop_done, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&x.pre_done, hipEventDisableTiming) != hipSuccess) { e->err = "event create failed"; return fail_create(MLDHIP_EHIP); }
 #endif
@@ -328,6 +341,8 @@ int mldhip_create(const mldhip_config* cfg, int device, mldhip_handle** out) {
   (void)hipFuncSetAttribute((const void*)gemm_pipe_x3_kernel<2, 4, 4, 4, 32, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (gemm_pipe_lds_bytes<2, 4, 4, 4>()));
   (void)hipFuncSetAttribute((const void*)den_loop_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLoopLdsBytes);
   (void)hipFuncSetAttribute((const void*)den_loop_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLoopLdsBytes);
+  (void)hipFuncSetAttribute((const void*)den_loop_kernel<false, kLoopEta>, hipFuncAttributeMaxDynamicSharedMemorySize, kLoopLdsBytes);
+  (void)hipFuncSetAttribute((const void*)den_loop_kernel<true, kLoopEta>, hipFuncAttributeMaxDynamicSharedMemorySize, kLoopLdsBytes);
 #if defined(MLDHIP_HOOKS)
   (void)hipFuncSetAttribute((const void*)den_loop_kernel<true, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, kLoopLdsBytes);
 #endif
@@ -335,6 +350,10 @@ int mldhip_create(const mldhip_config* cfg, int device, mldhip_handle** out) {
   (void)hipFuncSetAttribute((const void*)den_cluster_kernel<false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, kClLdsBytes);
   (void)hipFuncSetAttribute((const void*)den_cluster_kernel<true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, kClLdsBytes);
   (void)hipFuncSetAttribute((const void*)den_cluster_kernel<false, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, kClLdsBytes);
+  (void)hipFuncSetAttribute((const void*)den_cluster_eta_kernel<true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, kClLdsBytes);
+  (void)hipFuncSetAttribute((const void*)den_cluster_eta_kernel<false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, kClLdsBytes);
+  (void)hipFuncSetAttribute((const void*)den_cluster_eta_kernel<true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, kClLdsBytes);
+  (void)hipFuncSetAttribute((const void*)den_cluster_eta_kernel<false, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, kClLdsBytes);
 #define MLD_T32_ATTR1(MT, NS, TR, PR) \
   (void)hipFuncSetAttribute((const void*)gemm_tile32_kernel<MT, NS, TR, PR, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, kT32LdsBytes); \
   (void)hipFuncSetAttribute((const void*)gemm_tile32_kernel<MT, NS, TR, PR, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, kT32LdsBytes);
@@ -395,6 +414,7 @@ void mldhip_destroy(mldhip_handle* e) {
     if (x.lens) (void)hipFree(x.lens);
     if (x.lens2) (void)hipFree(x.lens2);
     if (x.labels) (void)hipFree(x.labels);
+    if (x.keys) (void)hipFree(x.keys);
   }
   if (e->trace_buf) (void)hipFree(e->trace_buf);
   if (e->nonfinite) (void)hipFree(e->nonfinite);
@@ -569,6 +589,9 @@ int denoiser_forward_impl(mldhip_handle* e, const float* sample_dev, int32_t tim
 // Range probe of the F16X3 mode (include/mldhip.h "Range contract"): the split-f16 kernels against the exact-fp32 ones of the SAME
 // handle on one seeded probe batch; a stage that disagrees (or is not finite) is switched to the fp32 kernels.
 int range_probe(mldhip_handle* e, hipStream_t stream, const float* user_text = nullptr, const float* user_lat = nullptr, int user_B = 0) {
+  // deterministic on every handle: the probe compares arithmetic on the eta = 0 step (include/mldhip.h "range_probe")
+  struct NoiseOff { mldhip_handle* e; bool v; ~NoiseOff() { e->noise_off = v; } } noise_off{e, e->noise_off};
+  e->noise_off = true;
   const int D = e->cfg.latent_dim, NF = e->cfg.nfeats, TD = e->cfg.text_dim;
   unsigned long long st = 0x9E3779B97F4A7C15ull;
   auto uni = [&]() { st = st * 6364136223846793005ull + 1442695040888963407ull; return (float)((st >> 40) + 1) * (1.0f / 16777217.0f); };
@@ -1053,6 +1076,17 @@ int sample_impl(mldhip_handle* e, const float* text_emb_dev, const int32_t* acti
 }  // namespace
 
 namespace {
+// The noise keys of a request's motions into the bound context's key array (stochastic DDIM, include/mldhip.h "Noise contract"): motion k of request i
+// gets {seed_i, first_index_i + k}; requests i0 .. i1 - 1 fill the array in chain order.  Stream-ordered like the lengths.
+int upload_keys(mldhip_handle* e, const mldhip_request* rq, const mldhip_noise_key* keys, int i0, int i1, hipStream_t stream) {
+  WsContext& x = e->ctxs[e->cur_ctx];
+  int o = 0;
+  for (int i = i0; i < i1; ++i)
+    for (int k = 0; k < rq[i].B; ++k, ++o) x.keys_host[o] = NoiseKey{(unsigned long long)keys[i].seed, (long long)keys[i].first_index + k};
+  HIP_TRY(e, hipMemcpyAsync(e->keys_dev, x.keys_host.data(), (size_t)o * sizeof(NoiseKey), hipMemcpyHostToDevice, stream));
+  return MLDHIP_OK;
+}
+
 // "many_pipeline": the requests of a mldhip_sample_many call ONE AFTER THE OTHER, each on the single-request path (the reverse loop of a request is one cluster
 // launch, kernels/loop_cluster.hpp) -- the reference's own shape, batch after batch (mld.py:618-672, test.py:116-119) -- with the two halves of consecutive requests
 // overlapped: the cluster launch holds 192 of 256 CUs at a few per cent of the matrix pipe for ~6.8 ms, the 44 decode launches of the previous request (one round
@@ -1063,7 +1097,8 @@ namespace {
 // Two workspaces alternate (request k + 2 waits for decode k).  D has the lowest stream priority: a cluster launch needs its workgroups resident together, the
 // decode's workgroups are short and independent of it -- they can only delay it, and they end.  The lane (ClusterLane) is held for the whole call; its event is
 // recorded on S behind the join.  Every request gets exactly what mldhip_sample gives it (same kernels, same graphs' machine code): bit-identical, tested.
-int sample_many_pipelined(mldhip_handle* e, const mldhip_request* rq, int nreq, const std::vector<int32_t>& tmax, hipStream_t stream) {
+int sample_many_pipelined(mldhip_handle* e, const mldhip_request* rq, int nreq, const std::vector<int32_t>& tmax, hipStream_t stream,
+                          const mldhip_noise_key* keys) {
   const bool action = is_action(e);
   const size_t D = e->cfg.latent_dim, NF = e->cfg.nfeats, TD = e->cfg.text_dim, NJ = (size_t)e->cfg.njoints * 3;
   ClusterLane lane(e, stream, e->cluster_lane);
@@ -1119,6 +1154,7 @@ int sample_many_pipelined(mldhip_handle* e, const mldhip_request* rq, int nreq, 
     }
     if (text) HIP_TRY(e, hipMemcpyAsync(e->text_in, text, (size_t)2 * r.B * TD * sizeof(float), hipMemcpyDeviceToDevice, prep));
     HIP_TRY(e, hipMemcpyAsync(e->lat_in, r.init_latents_dev, (size_t)r.B * D * sizeof(float), hipMemcpyDeviceToDevice, prep));
+    if (keys) if (int rc2 = upload_keys(e, rq, keys, i, i + 1, prep)) return rc2;
     if (split) {
       hipGraphExec_t pre = nullptr;
       GraphKey kp{r.B, 0, false, false}; kp.part = 1;
@@ -1183,6 +1219,7 @@ int sample_many_pipelined(mldhip_handle* e, const mldhip_request* rq, int nreq, 
       bind_context(e, k);
       if (std::find(used.begin(), used.end(), k) == used.end()) used.push_back(k);
       HIP_TRY(e, hipMemcpyAsync(e->lens_dev, r.lengths_host, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+      if (keys && (rc = upload_keys(e, rq, keys, i, i + 1, stream))) break;
       if (action) {
         HIP_TRY(e, hipMemsetAsync(e->labels_dev, 0, (size_t)B * sizeof(int32_t), stream));
         HIP_TRY(e, hipMemcpyAsync(e->labels_dev + B, r.actions_host, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, stream));
@@ -1212,7 +1249,7 @@ int sample_many_pipelined(mldhip_handle* e, const mldhip_request* rq, int nreq, 
 // the engine's staging buffers (unconditional halves first, as one big CFG batch), outputs scattered per request with
 // each request's own Tmax as its row pitch.  Motions never interact (attention is per sample), so results equal the
 // per-request calls up to the summation order of the kernel family picked for the larger row count.
-int sample_many_impl(mldhip_handle* e, const mldhip_request* rq, int nreq, hipStream_t stream) {
+int sample_many_impl(mldhip_handle* e, const mldhip_request* rq, int nreq, hipStream_t stream, const mldhip_noise_key* keys = nullptr) {
   if (!e->finalized) return e->fail(MLDHIP_ESTATE, "mldhip_sample_many before mldhip_finalize_weights");
   heal_cluster(e);
   const bool action = is_action(e);
@@ -1239,7 +1276,7 @@ int sample_many_impl(mldhip_handle* e, const mldhip_request* rq, int nreq, hipSt
   if (e->many_pipeline && nreq >= 2 && e->ctxs.size() >= 2) {
     bool ok = true;
     for (int i = 0; i < nreq; ++i) ok = ok && use_cluster(e, rq[i].B) && (rq[i].feats_out_dev || rq[i].joints_out_dev);
-    if (ok) return sample_many_pipelined(e, rq, nreq, tmax, stream);
+    if (ok) return sample_many_pipelined(e, rq, nreq, tmax, stream, keys);
   }
   if (Btot > e->cfg.max_batch) return e->fail(MLDHIP_EINVAL, "requests hold %d motions, max_batch is %d", Btot, e->cfg.max_batch);
   CtxUse use(e, stream);
@@ -1247,6 +1284,7 @@ int sample_many_impl(mldhip_handle* e, const mldhip_request* rq, int nreq, hipSt
   ClusterLane lane(e, stream, e->cluster_lane && use_cluster(e, Btot));
   const size_t D = e->cfg.latent_dim, NF = e->cfg.nfeats, TD = e->cfg.text_dim, NJ = (size_t)e->cfg.njoints * 3;
   HIP_TRY(e, hipMemcpyAsync(e->lens_dev, lens.data(), (size_t)Btot * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+  if (keys) if (int rc = upload_keys(e, rq, keys, 0, nreq, stream)) return rc;
   if (action) {
     std::vector<int32_t> lab(2 * (size_t)Btot, 0);        // cond = cat(zeros_like(actions), actions) (mld.py:722-725)
     int o = 0;
@@ -1300,12 +1338,29 @@ int sample_many_impl(mldhip_handle* e, const mldhip_request* rq, int nreq, hipSt
 
 extern "C" {
 
+// noise is never drawn from a fixed key behind the caller's back: an eta > 0 handle samples through the seeded entry point only
+#define MLDHIP_REFUSE_UNSEEDED(e, fn) \
+  if (eta_on(e)) return (e)->fail(MLDHIP_ESTATE, fn " on a handle with eta > 0 would draw its noise from a fixed key: use mldhip_sample_many_seeded (one mldhip_noise_key per request)")
+
 int mldhip_sample_many(mldhip_handle* e, const mldhip_request* reqs, int32_t nreq, void* stream_) {
   if (!e) return MLDHIP_EINVAL;
   DeviceGuard dg(e->device);
   if (is_novae(e)) return e->fail(MLDHIP_ESTATE, "mldhip_sample_many serves the latent models (text or action condition)");
+  MLDHIP_REFUSE_UNSEEDED(e, "mldhip_sample_many");
   if (!reqs || nreq < 1 || nreq > 64) return e->fail(MLDHIP_EINVAL, "1..64 requests expected");
   return sample_many_impl(e, reqs, nreq, (hipStream_t)stream_);
+}
+
+int mldhip_sample_many_seeded(mldhip_handle* e, const mldhip_request* reqs, const mldhip_noise_key* keys, int32_t nreq, void* stream_) {
+  if (!e) return MLDHIP_EINVAL;
+  DeviceGuard dg(e->device);
+  if (is_novae(e)) return e->fail(MLDHIP_ESTATE, "mldhip_sample_many_seeded serves the latent models (text or action condition)");
+  if (!reqs || nreq < 1 || nreq > 64) return e->fail(MLDHIP_EINVAL, "1..64 requests expected");
+  if (!keys) return e->fail(MLDHIP_EINVAL, "keys is NULL (one mldhip_noise_key per request)");
+  for (int i = 0; i < nreq; ++i)
+    if (keys[i].first_index < 0) return e->fail(MLDHIP_EINVAL, "keys[%d].first_index %lld is negative", i, (long long)keys[i].first_index);
+  // eta = 0: nothing is drawn -- the keys are ignored and the call IS mldhip_sample_many
+  return sample_many_impl(e, reqs, nreq, (hipStream_t)stream_, eta_on(e) ? keys : nullptr);
 }
 
 int mldhip_sample(mldhip_handle* e, const float* text_emb_dev, const float* init_latents_dev, const int32_t* lengths_host,
@@ -1314,6 +1369,7 @@ int mldhip_sample(mldhip_handle* e, const float* text_emb_dev, const float* init
   DeviceGuard dg(e->device);
   if (is_action(e)) return e->fail(MLDHIP_ESTATE, "engine was created with the action condition: use mldhip_sample_action");
   if (is_novae(e)) return e->fail(MLDHIP_ESTATE, "engine was created for the diffusion-only variant: use mldhip_sample_novae");
+  MLDHIP_REFUSE_UNSEEDED(e, "mldhip_sample");
   if (joints_out_dev && is_actor(e)) return e->fail(MLDHIP_ESTATE, "joints of the ActorVae feature layout need SMPL (out of scope)");
   if (!text_emb_dev) return e->fail(MLDHIP_EINVAL, "null input pointer");
   return sample_impl(e, text_emb_dev, nullptr, init_latents_dev, lengths_host, B, latents_out_dev, feats_out_dev, joints_out_dev, stream_);
@@ -1324,6 +1380,7 @@ int mldhip_sample_action(mldhip_handle* e, const int32_t* actions_host, const fl
   if (!e) return MLDHIP_EINVAL;
   DeviceGuard dg(e->device);
   if (!is_action(e)) return e->fail(MLDHIP_ESTATE, "engine was created with the text condition: use mldhip_sample");
+  MLDHIP_REFUSE_UNSEEDED(e, "mldhip_sample_action");
   if (!actions_host) return e->fail(MLDHIP_EINVAL, "null input pointer");
   return sample_impl(e, nullptr, actions_host, init_latents_dev, lengths_host, B, latents_out_dev, feats_out_dev, nullptr, stream_);
 }
@@ -1543,6 +1600,24 @@ int mldhip_vae_encode(mldhip_handle* e, const float* feats_dev, const int32_t* l
   return c.rc;
 }
 
+// stochastic DDIM step (mldhip_ddim_step_eta): one thread per Philox quad; z = noise[i] (injected) or element i of Philox(seed, step)
+__global__ void ddim_step_eta_kernel(const float* eps, const float* x, const float* noise, float* out, long long n, DdimCoef c, DdimEta k,
+                                     unsigned long long seed, unsigned step) {
+  const long long nq = (n + 3) / 4;
+  for (long long qd = (long long)blockIdx.x * blockDim.x + threadIdx.x; qd < nq; qd += (long long)gridDim.x * blockDim.x) {
+    float z[4] = {0.f, 0.f, 0.f, 0.f};
+    if (!noise) philox_normal4(seed, step, (unsigned long long)qd, z);
+    for (int j = 0; j < 4; ++j) {
+      const long long i = qd * 4 + j;
+      if (i >= n) break;
+      const float x0 = (x[i] - c.sqrt_1mat * eps[i]) / c.sqrt_at;
+      float y = c.sqrt_ap * x0 + k.c_eps * eps[i];
+      y += k.sigma * (noise ? noise[i] : z[j]);
+      out[i] = y;
+    }
+  }
+}
+
 __global__ void ddim_step_kernel(const float* eps, const float* x, float* out, long long n, DdimCoef c) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     const float x0 = (x[i] - c.sqrt_1mat * eps[i]) / c.sqrt_at;
@@ -1561,6 +1636,20 @@ int mldhip_ddim_step(mldhip_handle* e, const float* eps_dev, int32_t timestep, c
   MLD_LAUNCH(ddim_step_kernel, dim3((unsigned)std::min<int64_t>(1024, (n + 255) / 256)), dim3(256), 0, c.stream, eps_dev, sample_dev,
              prev_dev, (long long)n, ddim_coef(e, timestep));
   return check_launch(c, "ddim_step");
+}
+
+int mldhip_ddim_step_eta(mldhip_handle* e, const float* eps_dev, int32_t timestep, const float* sample_dev, const float* noise_dev,
+                         uint64_t seed, int32_t step_index, float* prev_dev, int64_t n, void* stream_) {
+  if (!e) return MLDHIP_EINVAL;
+  DeviceGuard dg(e->device);
+  if (is_ddpm(e)) return e->fail(MLDHIP_ESTATE, "engine was created with the DDPM scheduler: use mldhip_ddpm_step");
+  if (!eps_dev || !sample_dev || !prev_dev || n < 0 || step_index < 0) return e->fail(MLDHIP_EINVAL, "bad argument");
+  if (timestep < 0 || timestep >= e->cfg.num_train_timesteps) return e->fail(MLDHIP_EINVAL, "timestep %d out of range", timestep);
+  if (n == 0) return MLDHIP_OK;
+  Ctx c{e, (hipStream_t)stream_};
+  MLD_LAUNCH(ddim_step_eta_kernel, dim3((unsigned)std::min<int64_t>(1024, (n / 4 + 256) / 256)), dim3(256), 0, c.stream, eps_dev, sample_dev,
+             noise_dev, prev_dev, (long long)n, ddim_coef(e, timestep), ddim_eta(e, timestep), (unsigned long long)seed, (unsigned)step_index);
+  return check_launch(c, "ddim_step_eta");
 }
 
 int mldhip_feats2joints(mldhip_handle* e, const float* feats_dev, int32_t B, int32_t T, float* joints_out_dev, void* stream_) {

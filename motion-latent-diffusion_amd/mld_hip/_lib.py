@@ -14,7 +14,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(_HERE, "libmldhip.so")
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 
 class MldHipError(RuntimeError):
@@ -34,6 +34,7 @@ class Config(C.Structure):
         ("guidance_scale", C.c_float), ("precision", C.c_int32), ("use_graph", C.c_int32),
         ("condition", C.c_int32), ("nclasses", C.c_int32), ("vae_arch", C.c_int32), ("vae_num_layers", C.c_int32),
         ("denoiser_arch", C.c_int32), ("scheduler_type", C.c_int32), ("max_in_flight", C.c_int32),
+        ("eta", C.c_float),
     ]
 
 
@@ -42,6 +43,11 @@ class Request(C.Structure):
     _fields_ = [("text_emb_dev", C.c_void_p), ("actions_host", C.POINTER(C.c_int32)), ("init_latents_dev", C.c_void_p),
                 ("lengths_host", C.POINTER(C.c_int32)), ("B", C.c_int32), ("latents_out_dev", C.c_void_p),
                 ("feats_out_dev", C.c_void_p), ("joints_out_dev", C.c_void_p)]
+
+
+class NoiseKey(C.Structure):
+    """Mirror of ``mldhip_noise_key`` (include/mldhip.h "Noise contract"): the Philox seed of a request and the global index of its motion 0."""
+    _fields_ = [("seed", C.c_uint64), ("first_index", C.c_int64)]
 
 
 class NumericInfo(C.Structure):
@@ -73,6 +79,7 @@ _SYMBOLS = {
     "mldhip_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "mldhip_sample_many": (C.c_int, [C.c_void_p, C.POINTER(Request), C.c_int32, C.c_void_p]),
+    "mldhip_sample_many_seeded": (C.c_int, [C.c_void_p, C.POINTER(Request), C.POINTER(NoiseKey), C.c_int32, C.c_void_p]),
     "mldhip_denoiser_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "mldhip_sample_action": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
@@ -89,6 +96,8 @@ _SYMBOLS = {
     "mldhip_vae_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "mldhip_ddim_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "mldhip_ddim_step_eta": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p,
+                                       C.c_int64, C.c_void_p]),
     "mldhip_feats2joints": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "mldhip_get_timesteps": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]),
     "mldhip_get_alphas_cumprod": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int32]),
@@ -239,6 +248,19 @@ class Engine:
     def sample_many(self, requests: Sequence[dict], stream: int = 0):
         """Several requests as ONE chain (mldhip_sample_many).  Each request is a dict with ``lengths`` and ``init_latents``,
         ``text_emb`` (text engines) or ``actions`` (action engines), and optional ``latents_out`` / ``feats_out`` / ``joints_out``."""
+        arr, keep = self._requests(requests)
+        self._check(self.lib.mldhip_sample_many(self._h, arr, len(requests), stream))
+
+    def sample_many_seeded(self, requests: Sequence[dict], keys: Sequence, stream: int = 0):
+        """``sample_many`` with one noise key per request (mldhip_sample_many_seeded): ``keys[i]`` = ``(seed, first_index)``.  Required on an
+        eta > 0 handle; ignored (the call is ``sample_many``) on an eta = 0 one."""
+        if len(keys) != len(requests):
+            raise ValueError("one (seed, first_index) key per request")
+        arr, keep = self._requests(requests)
+        ks = (NoiseKey * len(keys))(*[NoiseKey(int(s) & 0xFFFFFFFFFFFFFFFF, int(f)) for s, f in keys])
+        self._check(self.lib.mldhip_sample_many_seeded(self._h, arr, ks, len(requests), stream))
+
+    def _requests(self, requests: Sequence[dict]):
         arr = (Request * len(requests))()
         keep = []
         for r, q in zip(arr, requests):
@@ -254,7 +276,7 @@ class Engine:
             r.latents_out_dev = _ptr(q.get("latents_out")) or None
             r.feats_out_dev = _ptr(q.get("feats_out")) or None
             r.joints_out_dev = _ptr(q.get("joints_out")) or None
-        self._check(self.lib.mldhip_sample_many(self._h, arr, len(requests), stream))
+        return arr, keep
 
     def denoiser_forward(self, sample, timestep: int, text_emb, R: int, out, stream: int = 0):
         self._check(self.lib.mldhip_denoiser_forward(self._h, _ptr(sample), int(timestep), _ptr(text_emb), R, _ptr(out), stream))
@@ -301,6 +323,11 @@ class Engine:
 
     def ddim_step(self, eps, timestep: int, sample, prev_sample, n: int, stream: int = 0):
         self._check(self.lib.mldhip_ddim_step(self._h, _ptr(eps), int(timestep), _ptr(sample), _ptr(prev_sample), n, stream))
+
+    def ddim_step_eta(self, eps, timestep: int, sample, noise, prev_sample, n: int, seed: int = 0, step_index: int = 0, stream: int = 0):
+        """DDIMScheduler.step with the handle's eta (mldhip_ddim_step_eta): ``noise`` [n] injected, or None for the Philox stream (seed, step_index)."""
+        self._check(self.lib.mldhip_ddim_step_eta(self._h, _ptr(eps), int(timestep), _ptr(sample), _ptr(noise), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                  int(step_index), _ptr(prev_sample), n, stream))
 
     def feats2joints(self, feats, B: int, T: int, joints_out, stream: int = 0):
         self._check(self.lib.mldhip_feats2joints(self._h, _ptr(feats), B, T, _ptr(joints_out), stream))

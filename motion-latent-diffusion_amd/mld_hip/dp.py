@@ -133,9 +133,11 @@ class DataParallelSampler:
         return max(1, min(nchunks, cap))
 
     def __call__(self, texts: Sequence[str] = None, lengths: Sequence[int] = None, actions: Sequence[int] = None, init_latents=None,
-                 step_noise=None):
+                 step_noise=None, seed: int = None):
         """step_noise (diffusion-only variant, optional): the DDPM scheduler's per-step draws [steps, N, Tmax, nfeats], indexed
-        like the prompts -- with `init_latents` it makes a motion independent of how the prompts are sharded and chunked."""
+        like the prompts -- with `init_latents` it makes a motion independent of how the prompts are sharded and chunked.
+        seed (stochastic DDIM, scheduler eta > 0): ONE Philox seed for the whole call; prompt k draws the noise keyed (seed, k) whatever
+        the world size, chunking or coalescing.  None = drawn from torch's default generator (seed torch identically on every rank)."""
         import torch.distributed as dist
         m = self.model
         action = getattr(m, "condition", None) == "action"
@@ -160,6 +162,9 @@ class DataParallelSampler:
         chunks = [(s, min(hi, s + self.batch_size)) for s in range(lo, hi, self.batch_size)]
         dev = next(m.parameters()).device
         novae = getattr(m, "vae_type", "") == "no"
+        if float(getattr(m, "eta", 0.0) or 0.0) > 0.0 and seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        kw = lambda s: {} if seed is None else {"seed": seed, "first_index": s}      # each chunk's global start index keys its motions
 
         def noise(s, e, ln):
             if init_latents is None:
@@ -184,7 +189,7 @@ class DataParallelSampler:
                 grp = chunks[g0:g0 + coalesce]
                 reqs = [([int(a) for a in actions[s:e]], [int(x) for x in lengths[s:e]]) for s, e in grp]
                 lats = [noise(s, e, ln) for (s, e), (_, ln) in zip(grp, reqs)] if init_latents is not None else None
-                for (feats, _), (_, ln) in zip(m.sample_many_action(reqs, init_latents=lats, device=dev), reqs):
+                for (feats, _), (_, ln) in zip(m.sample_many_action(reqs, init_latents=lats, device=dev, **kw(grp[0][0])), reqs):
                     f = feats.cpu()
                     out.extend(f[k, :n] for k, n in enumerate(ln))
             return list(range(lo, hi)), out
@@ -193,14 +198,14 @@ class DataParallelSampler:
                 ln = [int(x) for x in lengths[s:e]]
                 if action:
                     acts = [int(a) for a in actions[s:e]]
-                    rs = m.a2m_eval({"action": torch.tensor(acts, device=dev).reshape(-1, 1), "length": ln}, init_latents=noise(s, e, ln))
+                    rs = m.a2m_eval({"action": torch.tensor(acts, device=dev).reshape(-1, 1), "length": ln}, init_latents=noise(s, e, ln), **kw(s))
                     feats = rs["m_rst"].cpu()
                     out.extend(feats[k, :n] for k, n in enumerate(ln))
                 elif novae and step_noise is not None:
                     sn = step_noise[:, s:e, :max(ln)].to(dev).float().contiguous()
                     out.extend(m({"text": list(texts[s:e]), "length": ln}, init_latents=noise(s, e, ln), step_noise=sn))
                 else:
-                    out.extend(m({"text": list(texts[s:e]), "length": ln}, init_latents=noise(s, e, ln)))
+                    out.extend(m({"text": list(texts[s:e]), "length": ln}, init_latents=noise(s, e, ln), **kw(s)))
             return list(range(lo, hi)), out
         streams = [torch.cuda.Stream() for _ in range(self.in_flight)]
         for st in streams:
@@ -230,10 +235,10 @@ class DataParallelSampler:
                     reqs.append((m.text_encoder([""] * len(tx) + tx), ln))      # mld.py:224-231: unconditional half first
                     lats.append(noise(s, e, ln))
                 if len(reqs) == 1:
-                    joints, _, _ = m.sample(*reqs[0], init_latents=lats[0])
+                    joints, _, _ = m.sample(*reqs[0], init_latents=lats[0], **kw(grp[0][0]))
                     pending.append((joints, reqs[0][1]))
                 else:
-                    for (joints, _, _), (_, ln) in zip(m.sample_many(reqs, init_latents=lats if init_latents is not None else None), reqs):
+                    for (joints, _, _), (_, ln) in zip(m.sample_many(reqs, init_latents=lats if init_latents is not None else None, **kw(grp[0][0])), reqs):
                         pending.append((joints, ln))
         for st in streams:
             torch.cuda.current_stream().wait_stream(st)

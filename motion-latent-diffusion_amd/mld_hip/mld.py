@@ -68,6 +68,13 @@ class MLD(nn.Module):
         if hasattr(self.scheduler, "engine_config"):
             shared.update(self.scheduler.engine_config(cfg.model.scheduler.num_inference_timesteps))
         shared["guidance_scale"] = float(self.guidance_scale)
+        # scheduler.eta (configs/modules/scheduler.yaml:4): stochastic DDIM in the engine (include/mldhip.h "Noise contract")
+        try:
+            self.eta = float(cfg.model.scheduler.eta)
+        except (KeyError, AttributeError, TypeError):
+            self.eta = 0.0
+        if self.vae_type != "no":
+            shared["eta"] = self.eta
         for m in (self.denoiser, self.vae, datamodule, self.scheduler):
             if m is not None and hasattr(m, "_shared_arch") and engine_key is None:
                 m._shared_arch = shared
@@ -108,12 +115,25 @@ class MLD(nn.Module):
                                    "create the engine with mld_hip.engine.configure(**scheduler.engine_config(n)) first")
         if abs(eng.cfg.guidance_scale - self.guidance_scale) > 1e-6:
             raise RuntimeError("engine guidance_scale differs from cfg.model.guidance_scale")
+        if self.vae_type != "no" and abs(eng.cfg.eta - self.eta) > 1e-6:
+            raise RuntimeError(f"engine/scheduler mismatch on eta: engine {eng.cfg.eta}, scheduler {self.eta}; "
+                               "create the engine with mld_hip.engine.configure(eta=cfg.model.scheduler.eta) first")
         return eng
+
+    def _noise_seed(self, seed: Optional[int]) -> Optional[int]:
+        """The Philox seed of a fused stochastic-DDIM call (eta > 0): `seed`, or one drawn from torch's default CPU generator -- so
+        torch.manual_seed makes a run reproducible, as it does for the reference.  None at eta = 0 (nothing is drawn, the generator is untouched)."""
+        if self.eta == 0.0:
+            return None
+        return int(seed) if seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
 
     # ------------------------------------------------------------------ fused path
     @torch.no_grad()
-    def sample(self, text_emb: torch.Tensor, lengths: List[int], init_latents: Optional[torch.Tensor] = None):
-        """text_emb [2B, 1, 768] (uncond half first) -> (joints [B,T,22,3], feats [B,T,nfeats], latents [B,1,D]) on device."""
+    def sample(self, text_emb: torch.Tensor, lengths: List[int], init_latents: Optional[torch.Tensor] = None, seed: Optional[int] = None,
+               first_index: int = 0):
+        """text_emb [2B, 1, 768] (uncond half first) -> (joints [B,T,22,3], feats [B,T,nfeats], latents [B,1,D]) on device.
+        eta > 0: the step noise of motion m is the engine's Philox stream keyed (seed, first_index + m); `seed` None = drawn from torch's
+        generator."""
         lengths = [int(x) for x in lengths]
         B, T = len(lengths), max(lengths)
         dev = text_emb.device
@@ -129,11 +149,16 @@ class MLD(nn.Module):
         lat = torch.empty(B, self.latent_dim[0], self.latent_dim[-1], device=dev)
         feats = torch.empty(B, T, self.nfeats, device=dev)
         joints = torch.empty(B, T, self.njoints, 3, device=dev)
-        eng.sample(text_emb, init_latents, lengths, lat, feats, joints, _engine.current_stream_handle(text_emb))
+        seed = self._noise_seed(seed)
+        if seed is None:
+            eng.sample(text_emb, init_latents, lengths, lat, feats, joints, _engine.current_stream_handle(text_emb))
+        else:
+            eng.sample_many_seeded([dict(text_emb=text_emb, init_latents=init_latents, lengths=lengths, latents_out=lat, feats_out=feats,
+                                         joints_out=joints)], [(seed, int(first_index))], _engine.current_stream_handle(text_emb))
         return joints, feats, lat
 
     @torch.no_grad()
-    def sample_many(self, requests, init_latents=None, pipeline: bool = False):
+    def sample_many(self, requests, init_latents=None, pipeline: bool = False, seed: Optional[int] = None, first_index: int = 0):
         """Several independent text-to-motion requests as ONE engine call (``mldhip_sample_many``: one reverse-diffusion chain +
         one decode over all of them; the engine needs ``max_batch >= total motions``).  `requests` = [(text_emb [2B_i,1,768],
         lengths_i), ...]; returns [(joints_i, feats_i, latents_i), ...] on device, each shaped as ``sample`` would return it.
@@ -165,12 +190,24 @@ class MLD(nn.Module):
             outs.append((joints, feats, lat))
         if pipeline:
             eng.set_option("many_pipeline", 1)
+        seed = self._noise_seed(seed)
         try:
-            eng.sample_many(reqs, stream)
+            if seed is None:
+                eng.sample_many(reqs, stream)
+            else:       # motion k of request i is motion sum(B_<i) + k of the call: the same noise however the call is split
+                eng.sample_many_seeded(reqs, self._keys(seed, reqs, first_index), stream)
         finally:
             if pipeline:
                 eng.set_option("many_pipeline", 0)
         return outs
+
+    @staticmethod
+    def _keys(seed: int, reqs, first_index: int = 0):
+        out, o = [], int(first_index)
+        for q in reqs:
+            out.append((seed, o))
+            o += len(q["lengths"])
+        return out
 
     @torch.no_grad()
     def sample_novae(self, text_emb: torch.Tensor, lengths: List[int], init_latents: Optional[torch.Tensor] = None,
@@ -201,7 +238,8 @@ class MLD(nn.Module):
         return joints, feats
 
     @torch.no_grad()
-    def sample_action(self, actions, lengths: List[int], init_latents: Optional[torch.Tensor] = None, device=None):
+    def sample_action(self, actions, lengths: List[int], init_latents: Optional[torch.Tensor] = None, device=None, seed: Optional[int] = None,
+                      first_index: int = 0):
         """Action labels [B] / [B, 1] -> (feats [B, T, nfeats], latents [B, 1, D]) on device: ONE mldhip_sample_action call."""
         lengths = [int(x) for x in lengths]
         acts = [int(a) for a in (actions.reshape(-1).tolist() if torch.is_tensor(actions) else list(actions))]
@@ -213,11 +251,16 @@ class MLD(nn.Module):
         eng = self._engine()
         lat = torch.empty(B, self.latent_dim[0], self.latent_dim[-1], device=dev)
         feats = torch.empty(B, T, self.nfeats, device=dev)
-        eng.sample_action(acts, init_latents, lengths, lat, feats, _engine.current_stream_handle(init_latents))
+        seed = self._noise_seed(seed)
+        if seed is None:
+            eng.sample_action(acts, init_latents, lengths, lat, feats, _engine.current_stream_handle(init_latents))
+        else:
+            eng.sample_many_seeded([dict(actions=acts, init_latents=init_latents, lengths=lengths, latents_out=lat, feats_out=feats)], [(seed, int(first_index))],
+                                   _engine.current_stream_handle(init_latents))
         return feats, lat
 
     @torch.no_grad()
-    def sample_many_action(self, requests, init_latents=None, device=None):
+    def sample_many_action(self, requests, init_latents=None, device=None, seed: Optional[int] = None, first_index: int = 0):
         """Several action-to-motion requests as ONE engine call (``mldhip_sample_many`` with ``actions_host``): `requests` =
         [(actions_i, lengths_i), ...] -> [(feats_i [B_i, T_i, nfeats], latents_i), ...] on device; the engine needs
         ``max_batch >= total motions`` (four bs-256 requests per call: 30.0 k motions/s against 5.9 k one call at a time, bench.py)."""
@@ -238,18 +281,23 @@ class MLD(nn.Module):
             keep.append(lat0)
             reqs.append(dict(actions=acts, init_latents=lat0, lengths=lengths, latents_out=lat, feats_out=feats))
             outs.append((feats, lat))
-        eng.sample_many(reqs, _engine.current_stream_handle(keep[0]))
+        seed = self._noise_seed(seed)
+        if seed is None:
+            eng.sample_many(reqs, _engine.current_stream_handle(keep[0]))
+        else:
+            eng.sample_many_seeded(reqs, self._keys(seed, reqs, first_index), _engine.current_stream_handle(keep[0]))
         return outs
 
     @torch.no_grad()
-    def a2m_eval(self, batch, init_latents: Optional[torch.Tensor] = None):
+    def a2m_eval(self, batch, init_latents: Optional[torch.Tensor] = None, seed: Optional[int] = None, first_index: int = 0):
         """Sampling core of MLD.a2m_eval (mld.py:710-735): batch["action"] [B, 1] labels, batch["length"] -> rs_set with
         ``m_action`` / ``m_rst`` (features [B, T, nfeats]) / ``m_lens``.  The joints entries of the reference's rs_set go
         through SMPL (mld/transforms/rots2joints/smplh.py) and are not produced here."""
         actions, lengths = batch["action"], list(batch["length"])
         if self.fused:
+            noise_kw = {} if self.eta == 0.0 else {"seed": seed, "first_index": first_index}
             feats, _ = self.sample_action(actions, lengths, init_latents,
-                                          device=actions.device if torch.is_tensor(actions) and actions.is_cuda else None)
+                                          device=actions.device if torch.is_tensor(actions) and actions.is_cuda else None, **noise_kw)
         else:
             a = actions if torch.is_tensor(actions) else torch.tensor(actions)
             cond = torch.cat((torch.zeros_like(a), a)) if self.do_classifier_free_guidance else a      # mld.py:716-717
@@ -259,7 +307,11 @@ class MLD(nn.Module):
 
     # ------------------------------------------------------------------ reference surface
     @torch.no_grad()
-    def forward(self, batch, init_latents: Optional[torch.Tensor] = None, step_noise: Optional[torch.Tensor] = None):
+    def forward(self, batch, init_latents: Optional[torch.Tensor] = None, step_noise: Optional[torch.Tensor] = None, seed: Optional[int] = None,
+                first_index: int = 0):
+        """mld.py:216-265.  Stochastic DDIM (cfg.model.scheduler.eta > 0): the fused path draws the engine's Philox stream keyed (seed,
+        first_index + m) -- `seed` None = drawn from torch's generator; the modular path draws torch.randn, or takes step_noise [steps, B, 1, D]
+        (the fused path's draws reproduce it: include/mldhip.h "Noise contract")."""
         texts, lengths = list(batch["text"]), list(batch["length"])
         if self.do_classifier_free_guidance:                                    # mld.py:224-230: uncond half first
             texts = [""] * len(texts) + ([""] * len(texts) if self.condition == "text_uncond" else texts)
@@ -272,9 +324,10 @@ class MLD(nn.Module):
                 joints = self.feats2joints(z.permute(1, 0, 2).contiguous())     # mld.py:241-242: "decode" is a permute
             return remove_padding(joints.detach().cpu(), lengths)
         if self.fused:
-            joints, _, _ = self.sample(text_emb, lengths, init_latents)
+            noise_kw = {} if self.eta == 0.0 else {"seed": seed, "first_index": first_index}      # (eta = 0: the call of the deterministic path, unchanged)
+            joints, _, _ = self.sample(text_emb, lengths, init_latents, **noise_kw)
         else:
-            z = self._diffusion_reverse(text_emb, lengths, init_latents)
+            z = self._diffusion_reverse(text_emb, lengths, init_latents, step_noise)
             feats = self.vae.decode(z, lengths)
             joints = self.feats2joints(feats.detach())
         return remove_padding(joints.detach().cpu(), lengths)                   # mld.py:264-265
@@ -312,10 +365,12 @@ class MLD(nn.Module):
         extra = {}
         if "eta" in set(inspect.signature(self.scheduler.step).parameters.keys()):
             extra["eta"] = self.cfg.model.scheduler.eta
-        takes_noise = "noise" in set(inspect.signature(self.scheduler.step).parameters.keys())
+        params = set(inspect.signature(self.scheduler.step).parameters.keys())
+        # injected per-step draws: DDPM's `noise=`, DDIM's `variance_noise=` (eta > 0; diffusers draws torch.randn otherwise)
+        noise_kw = "noise" if "noise" in params else ("variance_noise" if "variance_noise" in params else None)
         for i, t in enumerate(self.scheduler.timesteps.tolist()):
-            if step_noise is not None and takes_noise:
-                extra["noise"] = step_noise[i]
+            if step_noise is not None and noise_kw:
+                extra[noise_kw] = step_noise[i]
             x = torch.cat([latents] * 2) if self.do_classifier_free_guidance else latents
             noise_pred = self.denoiser(sample=x, timestep=t, encoder_hidden_states=encoder_hidden_states,
                                        lengths=(list(lengths) * 2 if lengths is not None else None))[0]

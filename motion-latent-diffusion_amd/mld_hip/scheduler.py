@@ -2,7 +2,8 @@
 (configs/modules/scheduler.yaml:1-14; call sites mld.py:81-83,310-320,345-346).
 
 Third-party arithmetic restated from the published algorithm (diffusers is not installed; SURVEY.md App.
-A.3, parity unpinned): float32 tables, scaled_linear betas, steps_offset, set_alpha_to_one=False, eta=0.
+A.3, parity unpinned): float32 tables, scaled_linear betas, steps_offset, set_alpha_to_one=False, eta in [0, 1]
+(eta > 0: stochastic DDIM, sigma_t = eta sqrt((1 - ab_p) / (1 - ab_t) (1 - ab_t / ab_p)), noise added at every step).
 The tables are host logic.  ``step`` on device tensors goes through the C ABI (``mldhip_ddim_step`` / ``mldhip_ddpm_step`` of the
 engine of that device, whose tables are checked against this scheduler's fields by the registry); on CPU tensors it is the same
 four elementwise operations in torch (host logic, used by the CPU tests).  The fused ``MLD.sample`` never calls ``step``: the same
@@ -60,9 +61,16 @@ class HipDDIMScheduler:
         ts = (np.arange(0, num_inference_steps) * ratio).round()[::-1].copy().astype(np.int64) + self.config.steps_offset
         self.timesteps = torch.from_numpy(ts).to(device) if device is not None else torch.from_numpy(ts)
 
-    def step(self, model_output, timestep, sample, eta: float = 0.0, **kwargs):
-        if eta != 0.0:
-            raise NotImplementedError("eta > 0 draws noise inside the scheduler; MLD uses eta = 0 (scheduler.yaml:4)")
+    def step(self, model_output, timestep, sample, eta: float = 0.0, use_clipped_model_output: bool = False, generator=None,
+             variance_noise=None, **kwargs):
+        """diffusers.DDIMScheduler.step: x' = sqrt(ab_p) x0 + sqrt(1 - ab_p - sigma^2) eps + sigma z with sigma = eta sqrt(var).
+        eta > 0 draws z = ``variance_noise`` or ``torch.randn`` from ``generator`` -- on device tensors without either, from the device's
+        default generator, as diffusers does (the reference's own loop passes neither, mld.py:316-320,345-346).  The host mirror (CPU
+        tensors) draws no implicit noise: it needs ``variance_noise`` or ``generator``.  (``use_clipped_model_output`` only matters with
+        clip_sample, which is refused at construction.)"""
+        eta = float(eta)
+        if not 0.0 <= eta <= 1.0:
+            raise ValueError(f"eta={eta}: DDIM eta must be in [0, 1]")
         if self.num_inference_steps is None:
             raise ValueError("call set_timesteps() first")
         t = int(timestep)
@@ -72,18 +80,46 @@ class HipDDIMScheduler:
         sa, sb = float(a_t ** 0.5), float((1 - a_t) ** 0.5)
         pa, pb = float(a_p ** 0.5), float((1 - a_p) ** 0.5)
         x0 = (sample - sb * model_output) / sa
-        # device tensors: the step runs in libmldhip (mldhip_ddim_step) -- but only on the engine of the model this scheduler
-        # belongs to, and only while set_timesteps() agrees with that engine's grid: mldhip_ddim_step derives t_prev from the
-        # ENGINE's num_inference_steps.  A stand-alone scheduler, or one re-gridded with another step count, uses the torch
-        # arithmetic below (same formula) instead of instantiating an engine for an elementwise update.
+        if eta > 0.0 and variance_noise is None and generator is None and not sample.is_cuda:
+            raise NotImplementedError("eta > 0 on the host mirror (CPU tensors): pass variance_noise= or generator= (no implicit draw)")
+        if eta > 0.0 and variance_noise is None:
+            variance_noise = torch.randn(model_output.shape, generator=generator, dtype=model_output.dtype,
+                                         device=generator.device if generator is not None else model_output.device).to(model_output.device)
+        # device tensors: the step runs in libmldhip (mldhip_ddim_step / mldhip_ddim_step_eta) -- but only on the engine of the model this
+        # scheduler belongs to, only while set_timesteps() agrees with that engine's grid (the C side derives t_prev from the ENGINE's
+        # num_inference_steps) and, for eta > 0, only at the engine's eta (the handle's table).  A stand-alone scheduler, or one re-gridded
+        # with another step count or another eta, uses the torch arithmetic below (same formula) instead of instantiating an engine for an
+        # elementwise update.
         if (sample.is_cuda and sample.dtype == torch.float32 and model_output.dtype == torch.float32 and self._shared_arch
-                and self._shared_arch.get("num_inference_steps") == self.num_inference_steps):
+                and self._shared_arch.get("num_inference_steps") == self.num_inference_steps
+                and (eta == 0.0 or float(self._shared_arch.get("eta", 0.0)) == eta)):
             from . import engine as _engine
             eng = _engine.get_engine(sample.device, self._variant, want=self._shared_arch)
             out = torch.empty_like(sample, memory_format=torch.contiguous_format)
-            eng.ddim_step(model_output.contiguous(), t, sample.contiguous(), out, out.numel(), _engine.current_stream_handle(sample))
+            if eta == 0.0:
+                eng.ddim_step(model_output.contiguous(), t, sample.contiguous(), out, out.numel(), _engine.current_stream_handle(sample))
+            else:
+                z = variance_noise.to(device=sample.device, dtype=torch.float32).contiguous()
+                eng.ddim_step_eta(model_output.contiguous(), t, sample.contiguous(), z, out, out.numel(),
+                                  stream=_engine.current_stream_handle(sample))
             return SchedulerOutput(prev_sample=out, pred_original_sample=x0)
-        return SchedulerOutput(prev_sample=pa * x0 + pb * model_output, pred_original_sample=x0)
+        if eta == 0.0:
+            return SchedulerOutput(prev_sample=pa * x0 + pb * model_output, pred_original_sample=x0)
+        c_eps, sigma = self.eta_coeffs(t, eta)
+        prev_sample = pa * x0 + c_eps * model_output
+        prev_sample = prev_sample + sigma * variance_noise
+        return SchedulerOutput(prev_sample=prev_sample, pred_original_sample=x0)
+
+    def eta_coeffs(self, timestep: int, eta: float):
+        """(sqrt(1 - ab_p - sigma^2), sigma) of one step in float32, as diffusers computes them (the engine's second DDIM table)."""
+        f = np.float32
+        t = int(timestep)
+        prev = t - self.config.num_train_timesteps // self.num_inference_steps
+        a_t = f(self.alphas_cumprod[t].item())
+        a_p = f(self.alphas_cumprod[prev].item() if prev >= 0 else float(self.final_alpha_cumprod))
+        var = f(f(f(1.0) - a_p) / f(f(1.0) - a_t)) * f(f(1.0) - f(a_t / a_p))
+        sigma = f(f(eta) * np.sqrt(f(var), dtype=f))
+        return float(np.sqrt(max(f(f(f(1.0) - a_p) - f(sigma * sigma)), f(0.0)), dtype=f)), float(sigma)
 
     def add_noise(self, original_samples, noise, timesteps):
         a = self.alphas_cumprod.to(original_samples.device)[timesteps].reshape(-1, *([1] * (original_samples.dim() - 1)))
