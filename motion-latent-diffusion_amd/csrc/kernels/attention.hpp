@@ -164,10 +164,14 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const float* __res
 //        keys it already holds scores for -- 16kt + 4g + {0..3} of the two key tiles (2kb, 2kb + 1) -- so P needs no shuffle,
 //        and the matching V operand is two 8-byte reads of 4 consecutive keys each from the transposed planes.
 constexpr int kAttnX3KStride = 40;   // words per K row: 64 bf16 = 32 words + 8 pad (conflict-free ds_read_b128 at word 16c + 4g of key r, gemm.hpp kGemmLdsStride)
+// At 18 key tiles (T > 208) the K rows are padded by 4 words only (2-way conflicts on the K fragment reads): with 8, the two K planes of
+// 288 keys and the two V^T planes need 164 KiB, more than the 160 KiB of LDS a workgroup can have, and the launch is refused.
+template <int NKT>
+constexpr int attn_x3_kstride() { return NKT > 13 ? 36 : kAttnX3KStride; }
 template <int NKT>
 constexpr int attn_x3_vt_stride() { return ((NKT + 1) / 2) * 16 + 4; }   // words per V^T row: an even number of key tiles of 16 bf16 (= 8 words) + pad
 template <int NKT>
-constexpr int attn_x3_lds_bytes() { return (2 * NKT * 16 * kAttnX3KStride + 2 * 64 * attn_x3_vt_stride<NKT>()) * 4; }
+constexpr int attn_x3_lds_bytes() { return (2 * NKT * 16 * attn_x3_kstride<NKT>() + 2 * 64 * attn_x3_vt_stride<NKT>()) * 4; }
 
 __device__ __forceinline__ void split_hi_lo_x8(const float (&x)[8], U4& hi, U4& lo) {
   split16_pair(x[0], x[1], hi.x, lo.x);
@@ -187,7 +191,8 @@ __device__ __forceinline__ void split_hi_lo_x8_unit(const float (&x)[8], U4& hi,
 template <int NKT, int NW = 8>
 __global__ __launch_bounds__(NW * 64) void attn_decode_x3_kernel(const float* __restrict__ qkv, float* __restrict__ o,
                                                              const int* __restrict__ lens, int T, int H, int shared_qkv = 0) {
-  constexpr int HD = 64, KST = kAttnX3KStride, VST = attn_x3_vt_stride<NKT>(), NKB = (NKT + 1) / 2;
+  constexpr int HD = 64, KST = attn_x3_kstride<NKT>(), VST = attn_x3_vt_stride<NKT>(), NKB = (NKT + 1) / 2;
+  static_assert(attn_x3_lds_bytes<NKT>() <= 160 * 1024, "LDS of one workgroup: 160 KiB");
 #if defined(MLDHIP_SIM)
   unsigned* smem = reinterpret_cast<unsigned*>(hipsim::blk().dyn_smem.data());
 #else
