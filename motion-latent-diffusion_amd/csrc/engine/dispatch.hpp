@@ -1,6 +1,6 @@
 // Launch helpers: which GEMM tile / kernel instance a call maps to.
 // Part of libmldhip's single translation unit (included by ../mldhip.hip, in this order: state, params, dispatch,
-// path_latent, path_novae).  Internal linkage throughout (anonymous namespace) except the handle type itself.
+// path_latent, path_novae, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace) except the handle type itself.
 #pragma once
 
 namespace {

@@ -1,6 +1,6 @@
 // Latent-diffusion paths (configs 1-3, 5): denoiser loop, VAE decode / encode, feats2joints, sample() enqueue.
 // Part of libmldhip's single translation unit (included by ../mldhip.hip, in this order: state, params, dispatch,
-// path_latent, path_novae).  Internal linkage throughout (anonymous namespace) except the handle type itself.
+// path_latent, path_novae, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace) except the handle type itself.
 #pragma once
 
 namespace {

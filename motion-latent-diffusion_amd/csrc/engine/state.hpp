@@ -1,6 +1,6 @@
 // Engine state: parameter table entries, per-layer weight views, workspace contexts, the handle struct.
 // Part of libmldhip's single translation unit (included by ../mldhip.hip, in this order: state, params, dispatch,
-// path_latent, path_novae).  Internal linkage throughout (anonymous namespace) except the handle type itself.
+// path_latent, path_novae, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace) except the handle type itself.
 #pragma once
 
 namespace {
@@ -56,7 +56,10 @@ struct WsContext {
   std::map<GraphKey, hipGraphExec_t> graphs;   // captured sample() graphs of this workspace, evicted least-recently-used
   std::vector<GraphKey> graph_lru;             // most recent last
   std::map<std::tuple<int, int, int>, hipGraphExec_t> step_graphs;   // diffusion-only variant: (B, Tmax, chunk) -> captured DDPM steps
+  std::vector<hipEvent_t*> events() { return {&done, &loop_done, &pre_done}; }   // created with the context, destroyed with it (engine/create.hpp)
 #endif
+  // every device allocation the context owns: teardown frees what is listed HERE (a new buffer is added beside its declaration, nowhere else)
+  std::vector<void**> device_buffers() { return {(void**)&ws, (void**)&lens, (void**)&lens2, (void**)&labels, (void**)&keys}; }
 };
 
 struct mldhip_engine {
@@ -183,7 +186,14 @@ struct mldhip_engine {
   hipStream_t prep_stream = nullptr;   // "many_pipeline": the inputs, condition rows and flag clear of request k + 1 run here, beside the cluster launch of request k
   hipEvent_t many_start = nullptr;     // ... ordered behind what the caller's stream held when the call came in
   hipStream_t side_stream = nullptr;   // "many_pipeline": decodes run here, at the lowest stream priority (the cluster launch on the caller's stream gets its CUs first)
+  std::vector<hipStream_t*> streams() { return {&cap_stream, &side_stream, &prep_stream}; }   // owned: destroyed at teardown (engine/create.hpp destroy_engine)
+  std::vector<hipEvent_t*> events() { return {&many_start}; }
 #endif
+  // every device allocation the handle owns outside its contexts: teardown frees what is listed HERE (a new buffer is added beside its declaration, nowhere else)
+  std::vector<void**> device_buffers() {
+    return {(void**)&arena, (void**)&arena_x3, (void**)&ffn_streams, (void**)&loop_stream, (void**)&loop_stream_x3, (void**)&cl_stream,
+            (void**)&cl_wave_off_dev, (void**)&loop_small, (void**)&trace_buf, (void**)&nonfinite};
+  }
 
   int fail(int code, const char* fmt, ...) {
     char buf[1024];

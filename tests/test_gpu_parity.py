@@ -195,7 +195,7 @@ def test_cluster_loop_bs64_vs_reference_golden_and_launch_family(dev, golden_dir
     e = _lib.Engine(device=0, max_batch=64, max_frames=196, precision=1)
     _load(e)
     ns = e.numeric_status()
-    assert ns["probed"] == 1 and ns["loop_split_ok"] == 1, ns          # the probe ran the cluster kernel too (mldhip.hip range_probe (c))
+    assert ns["probed"] == 1 and ns["loop_split_ok"] == 1, ns          # the probe ran the cluster kernel too (engine/probe.hpp probe_loop_cluster)
     text, lat0 = _cuda(b.text_emb, dev), _cuda(b.init_latents, dev)
     lat, feats, joints = torch.empty(64, 1, 256, device=dev), torch.empty(64, 196, 263, device=dev), torch.empty(64, 196, 22, 3, device=dev)
     e.sample(text, lat0, b.lengths, lat, feats, joints)

@@ -743,7 +743,7 @@ def test_cluster_loop_two_skip_levels_sim():
     e = _lib.Engine(lib=simlib.sim_library(), use_graph=0, max_batch=8, max_frames=8, num_inference_steps=1, num_layers=5, precision=1)
     e.load_state_dict(sdd, "denoiser.")
     e.load_state_dict(syn.make_vae_state_dict(dims=dims), "vae.")
-    e.set_option("range_probe", 1)                           # finalize's probe runs the cluster loop too where the handle may pick it (probe (c), mldhip.hip)
+    e.set_option("range_probe", 1)                           # finalize's probe runs the cluster loop too where the handle may pick it (engine/probe.hpp probe_loop_cluster)
     e.set_option("cluster_max_batch", 8)
     e.finalize()
     ns = e.numeric_status()
