@@ -221,6 +221,12 @@ int mldhip_finalize_weights(mldhip_handle* h, void* stream);
  *                     zeros + the positional rows (mld_vae.py:216-222, actor_vae.py:221-222), the same for every sample, so Q, K, V of
  *                     layer 0 are computed for [T] rows and every (sample, head) attention workgroup reads them (exact: same numbers,
  *                     B times less work and no [B T][3 D] round trip through HBM for that layer); 0 = per sample like the other layers
+ *   "dec_lean"        F16X3 mode, chip-filling launches: 1 (default) = the decoder does not compute what the joints never read (results equal
+ *                     0 to the bit): a call in which no request asks for features ends in a 67-column final stage (the columns feats2joints
+ *                     reads; [M][68] staging rows instead of [M][263]); layer 0 takes its residual from the positional table and its
+ *                     attention output from ONE sample per distinct length (no per-sample copy of the positional rows, the other attention
+ *                     workgroups return at once); feats2joints counts the non-finite joints while it stores them (no separate pass).
+ *                     0 = the full feature row always, per-sample layer 0, the separate counting pass
  *   "dec_half"        F16X3 mode, decoder self-attention block, OPT-IN: 0 (default) = fp32 Q | K | V and split x3 products
  *                     (kernels/gemm_strip_x3.hpp, attention.hpp); 1 = in-projection on half rows x split weights, Q | K | V stored as halves
  *                     (q pre-scaled), attention on plain half operands (kernels/dec_half.hpp) -- kept only if finalize's probe reads the form below

@@ -446,11 +446,15 @@ int build_cluster_stream(Ctx& c) {
 
 // finalize-time (split precision modes): linear1 / linear2 of every decoder / encoder layer in the item order of
 // kernels/ffn_strip.hpp -- run1(0), then [run1(hb), run2(hb - 1)] for hb = 1..7, then run2(7) -- as split-f16 fragment images
+// feature columns feats2joints_kernel reads: 0 .. 3 (root) and 4 + 3 (j - 1) + {0, 1, 2} for the other joints -- 67 on HumanML3D
+int joint_feat_cols(const E* e) { return 4 + 3 * (e->cfg.njoints - 1); }
+
 int build_ffn_streams(Ctx& c) {
   E* e = c.e;
   e->ffn_stream_of.clear();
   e->gemm_stream_of.clear();
   e->final_stream = nullptr;
+  e->final_joints_stream = nullptr;
   if (e->ffn_streams) { (void)hipFree(e->ffn_streams); e->ffn_streams = nullptr; }
   const bool split = e->cfg.precision == MLDHIP_PREC_BF16X3_DECODE;
   if (!split || is_novae(e) || e->cfg.latent_dim != 256 || e->cfg.ff_size != 1024) return 0;
@@ -500,6 +504,15 @@ int build_ffn_streams(Ctx& c) {
         items.back().pad = std::min(128, NFv - blk * 128);     // valid rows of the block (pack_stream_rows_kernel zero-fills the rest)
       }
   }
+  // ... and block 0 cut to the rows feats2joints reads (joint_feat_cols), per chunk: the joints-only final stage (final_joints_x3_kernel)
+  const size_t joints_first = items.size();
+  if (items.size() > final_first && joint_feat_cols(e) <= std::min(128, NFv)) {
+    const float* wf = P(e, "vae.final_layer.weight");
+    for (int kc = 0; kc < 8; ++kc) {
+      push(wf, 256, 0, kc * 32);
+      items.back().pad = joint_feat_cols(e);
+    }
+  }
   LoopItem* items_dev = nullptr;
   if (hipMalloc((void**)&e->ffn_streams, items.size() * kLoopItemFloats * sizeof(float)) != hipSuccess ||
       hipMalloc((void**)&items_dev, items.size() * sizeof(LoopItem)) != hipSuccess)
@@ -520,6 +533,7 @@ int build_ffn_streams(Ctx& c) {
   for (size_t i = 0; i < layers.size(); ++i) e->ffn_stream_of[layers[i].first] = e->ffn_streams + i * (size_t)kFfnStripItems * kLoopItemFloats;
   for (auto& gf : gemm_first) e->gemm_stream_of[gf.first] = e->ffn_streams + gf.second * (size_t)kLoopItemFloats;
   if (items.size() > final_first) e->final_stream = e->ffn_streams + final_first * (size_t)kLoopItemFloats;
+  if (items.size() > joints_first) e->final_joints_stream = e->ffn_streams + joints_first * (size_t)kLoopItemFloats;
   return c.rc;
 }
 
@@ -557,7 +571,8 @@ void time_mlp(Ctx& c, const float* temb0, float* mid, float* out, int n) {
 int pick_nkt(int T) { return T <= 64 ? 4 : T <= 112 ? 7 : T <= 208 ? 13 : 18; }
 
 // shared_qkv: QKV holds ONE sample's projections [T][3D], read by every (sample, head) workgroup (decoder layer 0, dec_layer)
-void dec_attention(Ctx& c, int B, int T, const int32_t* lens = nullptr, int shared_qkv = 0) {
+// rep != nullptr (decoder layer 0 under "dec_lean"): only the samples that are their own representative compute (length_reps_kernel)
+void dec_attention(Ctx& c, int B, int T, const int32_t* lens = nullptr, int shared_qkv = 0, const int* rep = nullptr) {
   if (!lens) lens = c.e->lens_dev;
   E* e = c.e;
   const int H = e->cfg.num_heads;
@@ -571,16 +586,16 @@ void dec_attention(Ctx& c, int B, int T, const int32_t* lens = nullptr, int shar
     if (T <= 256 && (e->flash_attn == 2 || (e->flash_attn == 1 && B * H >= 512))) {
       // V staged row-major and read as MFMA fragments through ds_read_b64_tr_b16 (r03: 454 -> 417 us per launch at 2 048 motions against
       // transposed V planes written with 2-byte stores; streaming hints on its loads / stores measured level: both alternatives retired in r04)
-      MLD_LAUNCH(attn_flash_x3_kernel, grid, block, kFlashLdsBytes, c.stream, (const float*)e->QKV, e->AO, (const int*)lens, T, H, shared_qkv);
+      MLD_LAUNCH(attn_flash_x3_kernel, grid, block, kFlashLdsBytes, c.stream, (const float*)e->QKV, e->AO, (const int*)lens, T, H, shared_qkv, rep);
       count(c);
       check_launch(c, "attn_flash_x3");
       return;
     }
     switch (nkt) {
-      case 4: MLD_LAUNCH((attn_decode_x3_kernel<4>), grid, block, attn_x3_lds_bytes<4>(), c.stream, (const float*)e->QKV, e->AO, (const int*)lens, T, H, shared_qkv); break;
-      case 7: MLD_LAUNCH((attn_decode_x3_kernel<7>), grid, block, attn_x3_lds_bytes<7>(), c.stream, (const float*)e->QKV, e->AO, (const int*)lens, T, H, shared_qkv); break;
-      case 13: MLD_LAUNCH((attn_decode_x3_kernel<13>), grid, block, attn_x3_lds_bytes<13>(), c.stream, (const float*)e->QKV, e->AO, (const int*)lens, T, H, shared_qkv); break;
-      default: MLD_LAUNCH((attn_decode_x3_kernel<18>), grid, block, attn_x3_lds_bytes<18>(), c.stream, (const float*)e->QKV, e->AO, (const int*)lens, T, H, shared_qkv); break;
+      case 4: MLD_LAUNCH((attn_decode_x3_kernel<4>), grid, block, attn_x3_lds_bytes<4>(), c.stream, (const float*)e->QKV, e->AO, (const int*)lens, T, H, shared_qkv, rep); break;
+      case 7: MLD_LAUNCH((attn_decode_x3_kernel<7>), grid, block, attn_x3_lds_bytes<7>(), c.stream, (const float*)e->QKV, e->AO, (const int*)lens, T, H, shared_qkv, rep); break;
+      case 13: MLD_LAUNCH((attn_decode_x3_kernel<13>), grid, block, attn_x3_lds_bytes<13>(), c.stream, (const float*)e->QKV, e->AO, (const int*)lens, T, H, shared_qkv, rep); break;
+      default: MLD_LAUNCH((attn_decode_x3_kernel<18>), grid, block, attn_x3_lds_bytes<18>(), c.stream, (const float*)e->QKV, e->AO, (const int*)lens, T, H, shared_qkv, rep); break;
     }
     count(c);
     check_launch(c, "attn_decode_x3");
@@ -681,10 +696,23 @@ bool dec_half_on(const E* e, int T) {
 // the layer's Q, K, V depend on t only.  They are then projected once, for sample 0's T rows, and read by every (sample, head)
 // attention workgroup (which still applies its own sample's length mask): exact, and the [B T][3 D] tensor of that layer -- 1.23 GB
 // written and read back at 2 048 motions -- never exists ("dec_l0_once").
-void dec_layer(Ctx& c, int l, const float* xin, float* xout, int B, int T, bool pos_input = false) {
+// the rest of a decoder layer behind its self-attention as ONE launch (kernels/ffn_strip.hpp TAIL form, "dec_tail")
+bool dec_tail_on(E* e, const DecLayerP& L, int M) {
+  return e->dec_tail && staged_prec(e) == PREC_BF16X3 && e->strip_gemm && (e->ffn_strip == 3 || (e->ffn_strip == 1 && strip_rows_rt(e, M) == 6)) &&
+         e->cfg.latent_dim == 256 && e->cfg.ff_size == 1024 && !e->trace_on && M > e->small_m && e->ffn_stream_of.count(L.l1_w) && e->gemm_stream_of.count(L.out_w);
+}
+// "dec_lean", layer 0 where it runs through "dec_l0_once" and the fused tail: the positional table itself is the layer input (no init_queries copy
+// per sample: decode_body), the tail reads the attention output of each sample's length representative (dec_tail_l0_x3_kernel)
+bool dec_l0_lean(E* e, int B, int T) {
+  return e->dec_lean && e->dec_l0_once && B > 1 && T <= kMaxRepFrames && !e->dec.empty() && dec_tail_on(e, e->dec[0], B * T);
+}
+
+// lean (pos_input only): xin is the positional table [T][D] itself, see dec_l0_lean
+void dec_layer(Ctx& c, int l, const float* xin, float* xout, int B, int T, bool pos_input = false, bool lean = false) {
   E* e = c.e;
   const DecLayerP& L = e->dec[l];
   const int D = e->cfg.latent_dim, M = B * T;
+  const int* rep = lean ? reinterpret_cast<const int*>(e->len_rep) : nullptr;
   auto ragged = [&](GemmArgs g) { g.skip_lens = e->lens_dev; g.skip_rpg = T; return g; };   // skip all-padding row tiles
   const bool once = pos_input && e->dec_l0_once && B > 1;
   if (dec_half_on(e, T) && e->gemm_stream_of.count(L.in_w) && (once || M > e->small_m)) {
@@ -709,26 +737,26 @@ void dec_layer(Ctx& c, int l, const float* xin, float* xout, int B, int T, bool 
       count(c);
       check_launch(c, "strip_inproj_h");
     }
-    MLD_LAUNCH(attn_flash_h_kernel, dim3(B * e->cfg.num_heads), dim3(512), kFlashHLdsBytes, c.stream, (const unsigned*)qh, e->AO, (const int*)e->lens_dev, T, e->cfg.num_heads, once ? 1 : 0);
+    MLD_LAUNCH(attn_flash_h_kernel, dim3(B * e->cfg.num_heads), dim3(512), kFlashHLdsBytes, c.stream, (const unsigned*)qh, e->AO, (const int*)e->lens_dev, T, e->cfg.num_heads, once ? 1 : 0, rep);
     count(c);
     check_launch(c, "attn_flash_h");
   } else {
     // once: all T rows (no ragged skip: sample 0 may be shorter than the samples that read its rows)
     const GemmArgs q = once ? lin_args(xin, D, D, L.in_w, L.in_b, e->QKV, 3 * D, T, 3 * D) : ragged(lin_args(xin, D, D, L.in_w, L.in_b, e->QKV, 3 * D, M, 3 * D));
     if (!strip_gemm(c, q, false)) gemm(c, q);
-    dec_attention(c, B, T, nullptr, once ? 1 : 0);
+    dec_attention(c, B, T, nullptr, once ? 1 : 0, rep);
   }
   // Chip-filling launches of the split modes: the rest of the layer in ONE launch (kernels/ffn_strip.hpp, TAIL form) -- the H1 tensor
   // between the out-projection kernel and the feed-forward kernel is not written and read back ("dec_tail", on by default)
-  if (e->dec_tail && staged_prec(e) == PREC_BF16X3 && e->strip_gemm && (e->ffn_strip == 3 || (e->ffn_strip == 1 && strip_rows_rt(e, M) == 6)) &&
-      D == 256 && e->cfg.ff_size == 1024 && !e->trace_on && M > e->small_m && e->ffn_stream_of.count(L.l1_w) && e->gemm_stream_of.count(L.out_w)) {
+  if (dec_tail_on(e, L, M)) {
     FfnArgs a;
     a.W1 = e->ffn_stream_of[L.l1_w]; a.b1 = L.l1_b; a.b2 = L.l2_b; a.gamma = L.n3_w; a.beta = L.n3_b; a.Y = xout; a.M = M;
     a.skip_lens = e->lens_dev; a.skip_rpg = T;
     a.AO = e->AO; a.Wo = e->gemm_stream_of[L.out_w]; a.bo = L.out_b; a.res = xin; a.g1 = L.n1_w; a.be1 = L.n1_b;
     a.cvec = e->cvec + (size_t)l * e->cfg.max_batch * D; a.rpg = T; a.g2 = L.n2_w; a.be2 = L.n2_b;
     // (LDS images row-swizzled like the persistent loop's: 1 476 -> 1 457 us per launch at 2 048 motions, r04a; the plain-image build is retired)
-    MLD_LAUNCH((ffn_strip_x3_kernel<3, true, true>), dim3((M + 47) / 48), dim3(512), (ffn_strip_lds_bytes<3>()), c.stream, a);
+    if (lean) MLD_LAUNCH(dec_tail_l0_x3_kernel, dim3((M + 47) / 48), dim3(512), (ffn_strip_lds_bytes<3>()), c.stream, a, rep);      // a.res = the positional table
+    else MLD_LAUNCH((ffn_strip_x3_kernel<3, true, true>), dim3((M + 47) / 48), dim3(512), (ffn_strip_lds_bytes<3>()), c.stream, a);
     count(c);
     check_launch(c, "dec_tail_x3");
     return;
@@ -755,7 +783,9 @@ void skip_linear(Ctx& c, const std::string& prefix, int i, const float* x, const
 }
 
 // MldVae.decode (mld_vae.py:186-248).  z [B, D]; lens_dev already holds the lengths.
-void decode_body(Ctx& c, const float* z, int B, int T, float* feats_out) {
+// joints_only: nobody reads the features but feats2joints -- feats_out then receives [M][joints_pitch] rows (columns 0 .. 66 + padding) where the
+// joints-only final stage is built ("dec_lean"; *joints_pitch says which layout was written)
+void decode_body(Ctx& c, const float* z, int B, int T, float* feats_out, bool joints_only = false, int* joints_pitch = nullptr) {
   E* e = c.e;
   const int D = e->cfg.latent_dim, NF = e->cfg.nfeats, nb = (e->cfg.num_layers - 1) / 2, M = B * T;
   const int L = vae_layers(e);
@@ -770,19 +800,25 @@ void decode_body(Ctx& c, const float* z, int B, int T, float* feats_out) {
     o.sY = (long long)e->cfg.max_batch * D;
     gemm(c, o, L);
   }
-  {
-    // time queries = zeros + PE rows (learned: mld_vae.py:216-222; sinusoidal: actor_vae.py:221-222)
-    MLD_LAUNCH(init_queries_kernel, dim3(std::min(2048, (M * D / 4 + 255) / 256)), dim3(256), 0, c.stream, e->X0,
-               P(e, is_actor(e) ? "vae.decoder.sequence_pos_encoding.pe" : "vae.query_pos_decoder.pe"), B, T, D);
+  // time queries = zeros + PE rows (learned: mld_vae.py:216-222; sinusoidal: actor_vae.py:221-222)
+  const float* pe = P(e, is_actor(e) ? "vae.decoder.sequence_pos_encoding.pe" : "vae.query_pos_decoder.pe");
+  const bool lean0 = dec_l0_lean(e, B, T);
+  if (lean0) {
+    // layer 0 reads the table itself; what it needs per sample is the representative of its length (on device data: graphs stay keyed by shape)
+    MLD_LAUNCH(length_reps_kernel, dim3(1), dim3(256), 0, c.stream, (const int*)e->lens_dev, reinterpret_cast<int*>(e->len_rep), B, T);
+    count(c);
+    check_launch(c, "length_reps");
+  } else {
+    MLD_LAUNCH(init_queries_kernel, dim3(std::min(2048, (M * D / 4 + 255) / 256)), dim3(256), 0, c.stream, e->X0, pe, B, T, D);
     count(c);
     check_launch(c, "init_queries");
   }
   if (is_actor(e)) {
     // ActorAgnosticDecoder (actor_vae.py:224-235): plain stack, no skip links, no final LayerNorm
-    const float* xin = e->X0;
+    const float* xin = lean0 ? pe : e->X0;
     for (int l = 0; l < L; ++l) {
       float* xout = (l & 1) ? e->Hb : e->Ha;
-      dec_layer(c, l, xin, xout, B, T, l == 0);
+      dec_layer(c, l, xin, xout, B, T, l == 0, l == 0 && lean0);
       xin = xout;
     }
     GemmArgs f = lin_args(xin, D, D, P(e, "vae.decoder.final_layer.weight"), P(e, "vae.decoder.final_layer.bias"), feats_out, NF, M, NF);
@@ -790,12 +826,12 @@ void decode_body(Ctx& c, const float* z, int B, int T, float* feats_out) {
     gemm(c, f);
     return;
   }
-  const float* x = e->X0;
+  const float* x = lean0 ? pe : e->X0;
   for (int l = 0; l < nb; ++l) {
-    dec_layer(c, l, x, e->S[l], B, T, l == 0);
+    dec_layer(c, l, x, e->S[l], B, T, l == 0, l == 0 && lean0);
     x = e->S[l];
   }
-  dec_layer(c, nb, x, e->Ha, B, T, nb == 0);
+  dec_layer(c, nb, x, e->Ha, B, T, nb == 0, nb == 0 && lean0);
   for (int i = 0; i < nb; ++i) {
     skip_linear(c, "vae.decoder", i, e->Ha, e->S[nb - 1 - i], e->Hb, M, T);
     dec_layer(c, nb + 1 + i, e->Hb, e->Ha, B, T);
@@ -805,6 +841,15 @@ void decode_body(Ctx& c, const float* z, int B, int T, float* feats_out) {
     FinalStripArgs a;
     a.X = e->Ha; a.gamma = P(e, "vae.decoder.norm.weight"); a.beta = P(e, "vae.decoder.norm.bias"); a.W = e->final_stream;
     a.bias = P(e, "vae.final_layer.bias"); a.Y = feats_out; a.M = M; a.NF = NF; a.lens = e->lens_dev; a.rpg = T;
+    if (joints_only && e->dec_lean && e->final_joints_stream) {
+      // block 0 alone, rows of (67 + 1 pad) floats: the same chunk order and split products per column as the full kernel -> the same bits
+      a.W = e->final_joints_stream; a.NV = joint_feat_cols(e); a.NF = (a.NV + 3) / 4 * 4;
+      if (joints_pitch) *joints_pitch = a.NF;
+      MLD_LAUNCH(final_joints_x3_kernel, dim3((M + kFinalStripRows - 1) / kFinalStripRows), dim3(512), final_strip_lds_bytes(), c.stream, a);
+      count(c);
+      check_launch(c, "final_joints_x3");
+      return;
+    }
     MLD_LAUNCH(final_strip_x3_kernel, dim3((M + kFinalStripRows - 1) / kFinalStripRows), dim3(512), final_strip_lds_bytes(), c.stream, a);
     count(c);
     check_launch(c, "final_strip_x3");
@@ -888,14 +933,16 @@ void encode_body(Ctx& c, const float* feats, int B, int T, const float* eps, flo
   check_launch(c, "enc_finish");
 }
 
-void joints_body(Ctx& c, const float* feats, int B, int T, float* joints) {
+// pitch: floats between feature rows (0: nfeats); counter: where the kernel counts the non-finite joints it stores (nullptr: it does not)
+void joints_body(Ctx& c, const float* feats, int B, int T, float* joints, int pitch = 0, unsigned* counter = nullptr) {
   E* e = c.e;
+  if (pitch <= 0) pitch = e->cfg.nfeats;
   if (T <= 256) {
     MLD_LAUNCH((feats2joints_kernel<256>), dim3(B), dim3(256), 0, c.stream, feats, joints, P(e, "mean"), P(e, "std"), T,
-               e->cfg.nfeats, e->cfg.njoints);
+               pitch, e->cfg.njoints, counter);
   } else {
     MLD_LAUNCH((feats2joints_kernel<512>), dim3(B), dim3(256), 0, c.stream, feats, joints, P(e, "mean"), P(e, "std"), T,
-               e->cfg.nfeats, e->cfg.njoints);
+               pitch, e->cfg.njoints, counter);
   }
   count(c);
   check_launch(c, "feats2joints");
@@ -1008,12 +1055,16 @@ void launch_cluster_loop(Ctx& c, const float* init_lat, int B, int n, float guid
 void enqueue_decode(Ctx& c, int B, int T, float* feats_out, float* joints_out) {
   E* e = c.e;
   e->phase = 1;
+// feats_out == nullptr with joints_out set: nobody but feats2joints reads the features ("dec_lean": the narrow final stage)
   float* f = feats_out ? feats_out : e->feats_int;
-  decode_body(c, e->lat, B, T, f);
+  int pitch = 0;
+  decode_body(c, e->lat, B, T, f, !feats_out && joints_out, &pitch);
   if (joints_out) {
     e->phase = 2;
-    joints_body(c, f, B, T, joints_out);
-    count_nonfinite(c, joints_out, (long long)B * T * e->cfg.njoints * 3);
+    // "dec_lean": the joints kernel counts what it stores (the F16X3 range contract's run-time count, count_nonfinite)
+    unsigned* counter = e->dec_lean && e->cfg.precision == MLDHIP_PREC_BF16X3_DECODE ? e->nonfinite : nullptr;
+    joints_body(c, f, B, T, joints_out, pitch, counter);
+    if (!counter) count_nonfinite(c, joints_out, (long long)B * T * e->cfg.njoints * 3);
   } else {
     count_nonfinite(c, f, (long long)B * T * e->cfg.nfeats);      // feats-only call: the decoder's output is what the caller gets
   }

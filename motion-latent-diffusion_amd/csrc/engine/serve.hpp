@@ -112,7 +112,8 @@ int sample_impl(E* e, const float* text_emb_dev, const int32_t* actions_host, co
   // Calls served by the cluster loop replay a captured graph like the rest; its flags are cleared by a kernel, not a memset node: replays of
   // a hipMemsetAsync node in front of den_cluster_kernel left address-like words in the tail of the buffer on this runtime (r05).
   if (replays(e, B)) {
-    const bool want_j = joints_out_dev != nullptr, want_f = feats_out_dev != nullptr || want_j;
+    // want_f = the caller wants features; with "dec_lean" 0 the joints need the full feature row as well (the parent's keys)
+    const bool want_j = joints_out_dev != nullptr, want_f = feats_out_dev != nullptr || (want_j && !e->dec_lean);
     if (int rc = stage_inputs(e, text_emb_dev, init_latents_dev, B, stream)) return rc;
     hipGraphExec_t exec = nullptr;
     if (int rc = graph_for(e, GraphKey{B, T, want_f, want_j}, text_emb_dev != nullptr, &exec)) return rc;
@@ -272,7 +273,7 @@ int many_stage_pre(ManyCall& m, int i) {
 GraphKey many_decode_key(const ManyCall& m, int i) {
   const mldhip_request& r = m.rq[i];
   const bool want_j = r.joints_out_dev != nullptr;
-  GraphKey kd{r.B, m.tmax[i], r.feats_out_dev != nullptr || want_j, want_j};
+  GraphKey kd{r.B, m.tmax[i], r.feats_out_dev != nullptr || (want_j && !m.e->dec_lean), want_j};
   kd.dec_only = true;
   return kd;
 }
@@ -423,7 +424,7 @@ int sample_many_impl(E* e, const mldhip_request* rq, int nreq, hipStream_t strea
     Btot += r.B;
     T = std::max(T, tmax[i]);
     want_j = want_j || r.joints_out_dev;
-    want_f = want_f || r.feats_out_dev || r.joints_out_dev;
+    want_f = want_f || r.feats_out_dev || (r.joints_out_dev && !e->dec_lean);      // features for a caller (any request): the full [M][263] rows; joints alone do not need them ("dec_lean")
   }
   if (!e->group_ready[0] || !e->group_ready[1] || (want_j && !e->group_ready[2]))
     return e->fail(MLDHIP_ESTATE, "mldhip_sample_many needs denoiser.*, vae.decoder.* (and mean/std for joints) loaded");

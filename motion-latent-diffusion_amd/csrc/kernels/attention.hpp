@@ -190,7 +190,7 @@ __device__ __forceinline__ void split_hi_lo_x8_unit(const float (&x)[8], U4& hi,
 
 template <int NKT, int NW = 8>
 __global__ __launch_bounds__(NW * 64) void attn_decode_x3_kernel(const float* __restrict__ qkv, float* __restrict__ o,
-                                                             const int* __restrict__ lens, int T, int H, int shared_qkv = 0) {
+                                                             const int* __restrict__ lens, int T, int H, int shared_qkv = 0, const int* __restrict__ rep = nullptr) {
   constexpr int HD = 64, KST = attn_x3_kstride<NKT>(), VST = attn_x3_vt_stride<NKT>(), NKB = (NKT + 1) / 2;
   static_assert(attn_x3_lds_bytes<NKT>() <= 160 * 1024, "LDS of one workgroup: 160 KiB");
 #if defined(MLDHIP_SIM)
@@ -206,6 +206,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_x3_kernel(const float* __
   const int D = H * HD;
   const int b = blockIdx.x / H, h = blockIdx.x % H;
   const int bq = shared_qkv ? 0 : b;          // shared_qkv: every sample reads sample 0's projections (decoder layer 0: its input is the positional rows, the same for every sample)
+  if (rep && rep[b] != b) return;             // decoder layer 0, "dec_lean": another sample of this length computes these rows (length_reps_kernel); uniform per workgroup
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 15, g = lane >> 4;
   const int len = lens[b] < T ? lens[b] : T;
@@ -374,7 +375,7 @@ constexpr int kFlashLdsBytes = 2 * kFlashStageWords * 4;   // 40 960 B
 // planes with eight 2-byte stores per thread, 8-way bank conflicted: 454 vs 417 us per launch at 2 048 motions, same numbers to the bit;
 // streaming hints on the loads / stores measured level.  Both alternatives were retired in round 4.)
 __global__ __launch_bounds__(512, 4) void attn_flash_x3_kernel(const float* __restrict__ qkv, float* __restrict__ o,
-                                                            const int* __restrict__ lens, int T, int H, int shared_qkv = 0) {
+                                                            const int* __restrict__ lens, int T, int H, int shared_qkv = 0, const int* __restrict__ rep = nullptr) {
   constexpr int HD = 64, KST = kFlashKStride, VST = kFlashVStride, NW = 8;
 #if defined(MLDHIP_SIM)
   unsigned* smem = reinterpret_cast<unsigned*>(hipsim::blk().dyn_smem.data());
@@ -385,6 +386,7 @@ __global__ __launch_bounds__(512, 4) void attn_flash_x3_kernel(const float* __re
   const int D = H * HD;
   const int b = blockIdx.x / H, h = blockIdx.x % H;
   const int bq = shared_qkv ? 0 : b;          // shared_qkv: every sample reads sample 0's projections (decoder layer 0: its input is the positional rows, the same for every sample)
+  if (rep && rep[b] != b) return;             // decoder layer 0, "dec_lean": another sample of this length computes these rows (length_reps_kernel); uniform per workgroup
   const int tid = threadIdx.x, lane = tid & 63, wave = wave_uniform(tid >> 6);
   const int r = lane & 15, g = lane >> 4;
   const int len = lens[b] < T ? lens[b] : T;

@@ -162,7 +162,7 @@ constexpr int kFlashHStageWords = 2 * 32 * kFlashKStride;      // K plane + V pl
 constexpr int kFlashHLdsBytes = 2 * kFlashHStageWords * 4;     // 20 480 B
 
 __global__ __launch_bounds__(512, 4) void attn_flash_h_kernel(const unsigned* __restrict__ qkv, float* __restrict__ o,
-                                                           const int* __restrict__ lens, int T, int H, int shared_qkv) {
+                                                           const int* __restrict__ lens, int T, int H, int shared_qkv, const int* __restrict__ rep = nullptr) {
   constexpr int HD = 64, KST = kFlashKStride, NW = 8;
 #if defined(MLDHIP_SIM)
   unsigned* smem = reinterpret_cast<unsigned*>(hipsim::blk().dyn_smem.data());
@@ -173,6 +173,7 @@ __global__ __launch_bounds__(512, 4) void attn_flash_h_kernel(const unsigned* __
   const int D = H * HD, RW = 3 * D / 2;            // words per packed row
   const int b = blockIdx.x / H, h = blockIdx.x % H;
   const int bq = shared_qkv ? 0 : b;
+  if (rep && rep[b] != b) return;             // decoder layer 0, "dec_lean": another sample of this length computes these rows (length_reps_kernel); uniform per workgroup
   const int tid = threadIdx.x, lane = tid & 63, wave = wave_uniform(tid >> 6);
   const int r = lane & 15, g = lane >> 4;
   const int len = lens[b] < T ? lens[b] : T;

@@ -92,6 +92,32 @@ __global__ __launch_bounds__(256) void init_queries_kernel(float* __restrict__ H
   }
 }
 
+// Decoder layer 0 ("dec_lean"): its self-attention output depends on (frame, length of the sample) only, so one sample per distinct
+// length computes it: rep[b] = the smallest b' with lens[b'] == lens[b] (lengths clamped to T, as the attention kernels clamp them).
+// One workgroup: a table over the lengths 0 .. T in LDS filled with atomicMin (deterministic: a minimum), then one read per sample.
+constexpr int kMaxRepFrames = 1024;
+__global__ __launch_bounds__(256) void length_reps_kernel(const int* __restrict__ lens, int* __restrict__ rep, int B, int T) {
+  __shared__ int first[kMaxRepFrames + 1];
+  const int tid = threadIdx.x;
+  for (int l = tid; l <= T; l += 256) first[l] = B;
+  __syncthreads();
+  for (int b = tid; b < B; b += 256) {
+    int l = lens[b] < T ? lens[b] : T;
+    l = l > 0 ? l : 0;
+#if defined(MLDHIP_SIM)
+    if (b < first[l]) first[l] = b;
+#else
+    atomicMin(&first[l], b);
+#endif
+  }
+  __syncthreads();
+  for (int b = tid; b < B; b += 256) {
+    int l = lens[b] < T ? lens[b] : T;
+    l = l > 0 ? l : 0;
+    rep[b] = first[l];
+  }
+}
+
 __global__ __launch_bounds__(256) void add_rows_kernel(float* __restrict__ dst, const float* __restrict__ a,
                                                        const float* __restrict__ vec, int rows, int D) {
   // dst[r][d] = a[r][d] + vec[d]
@@ -255,10 +281,13 @@ __global__ __launch_bounds__(256) void count_nonfinite_kernel(const float* __res
   }
 }
 
+// `nfeats` is the row pitch of `feats` and nothing else: the full [..][263] features, or the 68-float rows of the joints-only final
+// stage (final_strip.hpp final_joints_x3_kernel).  `counter` != nullptr: the non-finite values among the joints are counted as they
+// are stored (count_nonfinite_kernel's per-wave sum and atomic), so the joints are not read back by a pass of their own.
 template <int MAXT>
 __global__ __launch_bounds__(256) void feats2joints_kernel(const float* __restrict__ feats, float* __restrict__ joints,
                                                            const float* __restrict__ mean, const float* __restrict__ stdv,
-                                                           int T, int nfeats, int njoints) {
+                                                           int T, int nfeats, int njoints, unsigned* __restrict__ counter = nullptr) {
   __shared__ float s_cos[MAXT], s_sin[MAXT], s_rx[MAXT], s_rz[MAXT];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   const float* F = feats + (long long)b * T * nfeats;
@@ -316,14 +345,17 @@ __global__ __launch_bounds__(256) void feats2joints_kernel(const float* __restri
   }
   __syncthreads();
   const int total = T * njoints;
+  float bad = 0.f;
+  auto nonfinite = [](float v) { return ((__builtin_bit_cast(unsigned, v) & 0x7F800000u) == 0x7F800000u) ? 1.f : 0.f; };
   for (int idx = tid; idx < total; idx += 256) {
     const int t = idx / njoints, j = idx - t * njoints;
     float* out = joints + ((long long)(b * T + t) * njoints + j) * 3;
     const float rx = s_rx[t], rz = s_rz[t];
+    float o0, o1, o2;
     if (j == 0) {
-      out[0] = rx;
-      out[1] = F[(long long)t * nfeats + 3] * stdv[3] + mean[3];
-      out[2] = rz;
+      o0 = rx;
+      o1 = F[(long long)t * nfeats + 3] * stdv[3] + mean[3];
+      o2 = rz;
     } else {
       const int c0 = 4 + (j - 1) * 3;
       const float px = F[(long long)t * nfeats + c0] * stdv[c0] + mean[c0];
@@ -332,9 +364,21 @@ __global__ __launch_bounds__(256) void feats2joints_kernel(const float* __restri
       const float c = s_cos[t], s = s_sin[t];
       const float uvx = -s * pz, uvz = s * px;
       const float uuvx = -s * uvz, uuvz = s * uvx;
-      out[0] = px + 2.f * (c * uvx + uuvx) + rx;
-      out[1] = py;
-      out[2] = pz + 2.f * (c * uvz + uuvz) + rz;
+      o0 = px + 2.f * (c * uvx + uuvx) + rx;
+      o1 = py;
+      o2 = pz + 2.f * (c * uvz + uuvz) + rz;
+    }
+    out[0] = o0; out[1] = o1; out[2] = o2;
+    bad += nonfinite(o0) + nonfinite(o1) + nonfinite(o2);
+  }
+  if (counter) {                                 // (uniform: a kernel argument)
+    bad = sum64(bad);
+    if (lane == 0 && bad > 0.f) {
+#if defined(MLDHIP_SIM)
+      *counter += (unsigned)bad;
+#else
+      atomicAdd(counter, (unsigned)bad);
+#endif
     }
   }
 }

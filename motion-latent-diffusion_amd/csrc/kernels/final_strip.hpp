@@ -22,6 +22,7 @@ struct FinalStripArgs {
   float* Y = nullptr;                // [M][NF]
   int M = 0, NF = 0;
   const int* lens = nullptr; int rpg = 1;      // rows with (row % rpg) >= lens[row / rpg] are written as zeros
+  int NV = 0;                        // final_joints_x3_kernel: valid output columns (bias entries); Y rows are NF >= NV floats apart, the rest zeros
 };
 
 constexpr int kFinalStripRows = 48, kFinalStripItems = 24;
@@ -47,9 +48,11 @@ __global__ __launch_bounds__(512) void pack_stream_rows_kernel(const float* __re
   *reinterpret_cast<U4*>(dst + 4) = lo;
 }
 
-// grid = ceil(M / 48); block = 512
-__global__ __launch_bounds__(512, 4) void final_strip_x3_kernel(FinalStripArgs p) {
-  constexpr int RT = 3, BM = RT * 16, XS = kFsXs;
+// NB = column blocks of 128: 3 = the whole feature row (final_strip_x3_kernel), 1 = block 0 alone (final_joints_x3_kernel: the stream holds
+// [chunk][block 0] only).  A column's accumulator sees the same products in the same order in both: columns of block 0 agree to the bit.
+template <int NB>
+__device__ __forceinline__ void final_strip_body(const FinalStripArgs& p) {
+  constexpr int RT = 3, BM = RT * 16, XS = kFsXs, kItems = 8 * NB;
 #if defined(MLDHIP_SIM)
   float* smem = reinterpret_cast<float*>(hipsim::blk().dyn_smem.data());
 #else
@@ -68,7 +71,7 @@ __global__ __launch_bounds__(512, 4) void final_strip_x3_kernel(FinalStripArgs p
   F4 ring[RING][2];
   int gitem = 0;
   auto gload = [&](int slot) __attribute__((always_inline)) {
-    const int it = gitem < kFinalStripItems ? gitem : kFinalStripItems - 1;      // past the end: a redundant load, never multiplied
+    const int it = gitem < kItems ? gitem : kItems - 1;      // past the end: a redundant load, never multiplied
     const float* s = gsrc + (unsigned)it * (unsigned)kLoopItemFloats;
     ring[slot][0] = ld4(s);
     ring[slot][1] = ld4(s + 4);
@@ -117,10 +120,10 @@ __global__ __launch_bounds__(512, 4) void final_strip_x3_kernel(FinalStripArgs p
   }
   __syncthreads();
 
-  // ---- products: 8 chunks x 3 column blocks
-  f32x4 acc[3][RT];
+  // ---- products: 8 chunks x NB column blocks
+  f32x4 acc[NB][RT];
 #pragma unroll
-  for (int b = 0; b < 3; ++b)
+  for (int b = 0; b < NB; ++b)
 #pragma unroll
     for (int t = 0; t < RT; ++t) acc[b][t] = f32x4{0.f, 0.f, 0.f, 0.f};
   const float* xa = Xs + r * XS + g * 4;
@@ -130,8 +133,8 @@ __global__ __launch_bounds__(512, 4) void final_strip_x3_kernel(FinalStripArgs p
 #pragma unroll
     for (int t = 0; t < RT; ++t) { x[t][0] = ld4(xa + t * 16 * XS + 32 * c); x[t][1] = ld4(xa + t * 16 * XS + 32 * c + 16); }
 #pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      const int slot = (3 * c + b) % RING;
+    for (int b = 0; b < NB; ++b) {
+      const int slot = (NB * c + b) % RING;
       const U4 wh = __builtin_bit_cast(U4, ring[slot][0]), wl = __builtin_bit_cast(U4, ring[slot][1]);
 #pragma unroll
       for (int t = 0; t < RT; ++t) acc[b][t] = mfma_x3_16x16x32(__builtin_bit_cast(U4, x[t][1]), wh, acc[b][t]);
@@ -148,9 +151,11 @@ __global__ __launch_bounds__(512, 4) void final_strip_x3_kernel(FinalStripArgs p
   // ---- bias, padded-frame zeroing, results parked row-major [48][NF] PACKED (row stride NF): the strip's output block as it lies in memory
   float* Out = Xs;                                         // 48 NF <= 48 x 264 floats (the engine builds the stream only for NF <= 264)
 #pragma unroll
-  for (int b = 0; b < 3; ++b) {
+  for (int b = 0; b < NB; ++b) {
     const int col = b * 128 + col0;
-    const float bi = p.bias[col < p.NF ? col : p.NF - 1];
+    float bi;
+    if constexpr (NB == 3) bi = p.bias[col < p.NF ? col : p.NF - 1];
+    else bi = col < p.NV ? p.bias[col] : 0.f;            // pad columns NV .. NF - 1: zero weight rows, no bias -> zeros
     if (col < p.NF) {
 #pragma unroll
       for (int t = 0; t < RT; ++t)
@@ -174,5 +179,13 @@ __global__ __launch_bounds__(512, 4) void final_strip_x3_kernel(FinalStripArgs p
     }
   }
 }
+
+// grid = ceil(M / 48); block = 512
+__global__ __launch_bounds__(512, 4) void final_strip_x3_kernel(FinalStripArgs p) { final_strip_body<3>(p); }
+
+// The joints-only end of the decoder ("dec_lean"): feats2joints reads feature columns 0 .. 66 and nothing else, so a call nobody asks features
+// of multiplies block 0 alone (rows 0 .. NV - 1 of the weight, zero-padded to 128: a third of the matrix instructions) and writes [M][NF = 68]
+// staging rows (NV = 67 columns + one pad: rows stay 16-byte aligned; a quarter of the store), which feats2joints_kernel reads with 68 as its pitch.
+__global__ __launch_bounds__(512, 4) void final_joints_x3_kernel(FinalStripArgs p) { final_strip_body<1>(p); }
 
 }  // namespace mld

@@ -197,6 +197,9 @@ int mldhip_set_option(mldhip_handle* e, const char* name, int64_t value) {
   } else if (n == "dec_l0_once") {
     if (value != 0 && value != 1) return e->fail(MLDHIP_EINVAL, "dec_l0_once must be 0 or 1");
     e->dec_l0_once = (int)value;
+  } else if (n == "dec_lean") {
+    if (value != 0 && value != 1) return e->fail(MLDHIP_EINVAL, "dec_lean must be 0 or 1");
+    e->dec_lean = (int)value;
   } else if (n == "many_pipeline") {
     if (value != 0 && value != 1) return e->fail(MLDHIP_EINVAL, "many_pipeline must be 0 (one chain over all motions of a mldhip_sample_many call) or 1 (request after request, decodes on the side stream)");
     if (value && e->ctxs.size() < 2) return e->fail(MLDHIP_EINVAL, "many_pipeline needs two workspaces: create the handle with max_in_flight >= 2");
