@@ -34,7 +34,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define MLDHIP_ABI_VERSION 6
+#define MLDHIP_ABI_VERSION 7
 
 enum {
   MLDHIP_OK = 0,
@@ -115,6 +115,16 @@ typedef struct mldhip_config {
                                  * (the "Noise contract" below).  Read only when struct_size covers it (an ABI-5 caller's smaller struct means 0).
                                  * mldhip_create refuses eta < 0, eta > 1, NaN, and eta != 0 with MLDHIP_SCHED_DDPM.  A handle with eta > 0 samples
                                  * through mldhip_sample_many_seeded only: mldhip_sample / _action / _many fail with MLDHIP_ESTATE. */
+  /* ---- ABI 7: the optional CLIP text tower (mldhip_text_encode below; transformers CLIPTextConfig of the model at configs/assets.yaml model.clip_path).
+   * Read only when struct_size covers them (an ABI-6 caller's smaller struct means no tower).  The tower's width is text_dim.  With clip_layers > 0
+   * mldhip_create refuses text_dim / clip_heads != 64, clip_ctx > 80, non-positive sizes, widths other than text_dim 768 / clip_ff 3072 (what the
+   * GEMMs are built for) and MLDHIP_PREC_BF16. */
+  int32_t clip_layers;          /* num_hidden_layers = 12; 0 (default) = no tower: no weights, no workspace, every text_encoder.* key ignored */
+  int32_t clip_heads;           /* num_attention_heads = 12 */
+  int32_t clip_ff;              /* intermediate_size = 3072 */
+  int32_t clip_vocab;           /* vocab_size = 49408 */
+  int32_t clip_ctx;             /* max_position_embeddings = 77 */
+  int32_t clip_max_prompts;     /* capacity: prompts per mldhip_text_encode call; 0 (default) = 2 x max_batch (one classifier-free-guidance batch) */
 } mldhip_config;
 
 enum { MLDHIP_COND_TEXT = 0, MLDHIP_COND_ACTION = 1 };
@@ -137,7 +147,11 @@ void mldhip_destroy(mldhip_handle* h);
  * ("denoiser.encoder.input_blocks.0.self_attn.in_proj_weight", "vae.final_layer.bias", ...) or
  * "mean" / "std".  Keys the engine never reads (denoiser.mem_pos.pe, text_encoder.*, t2m_*) are accepted
  * and ignored (returns 1).  Weight groups (denoiser.*, VAE decoder, VAE encoder, mean/std) are each
- * all-or-nothing; ops of an absent group return MLDHIP_ESTATE.  `src_is_device` != 0 when `data` is a device pointer. */
+ * all-or-nothing; ops of an absent group return MLDHIP_ESTATE.  `src_is_device` != 0 when `data` is a device pointer.
+ * With clip_layers > 0 the text tower's tensors form one more optional group (all-or-nothing, like vae.encoder.*):
+ *   text_encoder.text_model.text_model.embeddings.{token,position}_embedding.weight, ...encoder.layers.{i}.{layer_norm1,layer_norm2}.{weight,bias},
+ *   ...self_attn.{q,k,v,out}_proj.{weight,bias}, ...mlp.{fc1,fc2}.{weight,bias}, ...final_layer_norm.{weight,bias}, text_encoder.text_model.text_projection.weight;
+ * every other text_encoder.* key (vision_model.*, visual_projection, logit_scale, position_ids) stays accepted and ignored. */
 int mldhip_load_tensor(mldhip_handle* h, const char* key, const void* data, const int64_t* shape,
                        int32_t ndim, int32_t dtype, int32_t src_is_device);
 
@@ -448,6 +462,26 @@ int mldhip_ddim_step(mldhip_handle* h, const float* eps_dev, int32_t timestep, c
  * (the Noise contract with first_index 0).  n elements, in/out may alias. */
 int mldhip_ddim_step_eta(mldhip_handle* h, const float* eps_dev, int32_t timestep, const float* sample_dev, const float* noise_dev,
                          uint64_t seed, int32_t step_index, float* prev_sample_dev, int64_t n, void* stream);
+
+/* The CLIP text tower (ABI 7; handles created with clip_layers > 0).  Replaces: the text branch of MldTextEncoder.forward behind the tokenizer
+ * (mld/models/architectures/mld_clip.py:53-78: text_model.get_text_features(input_ids) -> unsqueeze(1)), i.e. transformers' CLIPModel.get_text_features:
+ * token + position embedding, clip_layers pre-LN layers (layer_norm1, causal self-attention with q scaled by head_dim^-0.5, residual, layer_norm2, fc1,
+ * quick-GELU x * sigmoid(1.702 x), fc2, residual), final_layer_norm, the EOS row, text_projection (no bias).
+ *   ids_host          [P][clip_ctx] token ids as the tokenizer pads them (every id in [0, clip_vocab))
+ *   eos_pos_host      [P] position of the EOS token in [0, clip_ctx) (CLIPTextTransformer's pooling rule; the tokenizer stays on the CPU)
+ *   text_emb_out_dev  [P][1][text_dim]
+ * Exactness rules -- each computes the numbers of the padded [P][clip_ctx] tower, on less work:
+ *   1. causality: the attention is causal and the output is read at the EOS row, so ids behind eos_pos never reach it -- they are not read, and prompt p
+ *      runs as eos_pos[p] + 1 token rows (all prompts of a call packed into one ragged activation; no padding rows exist);
+ *   2. duplicates: identical (ids[0 .. eos_pos], eos_pos) rows of a call -- the B copies of "" of a classifier-free-guidance batch -- are computed once
+ *      and stored to every duplicate's output row (deduplicated on the host, on the id rows);
+ *   3. the last stage: final_layer_norm and the projection run on the EOS rows only.
+ * A prompt's output row is bit-identical whatever else is in the call.  Arithmetic: the handle's mode (MLDHIP_PREC_F32 exact-fp32 MFMAs,
+ * MLDHIP_PREC_F16X3 split-f16 GEMMs and attention products; fp32 LayerNorm, softmax, residuals).  Issued eagerly (no hipGraph: the row total changes
+ * per call), stream-ordered like every other call; non-finite output values are counted into mldhip_numeric_status like latents and joints.
+ * Returns MLDHIP_EINVAL for P > clip_max_prompts, an id outside [0, clip_vocab) or eos_pos outside [0, clip_ctx); MLDHIP_ESTATE when the handle has no
+ * tower (clip_layers = 0), the tower's weight group is absent, or the handle is not finalized. */
+int mldhip_text_encode(mldhip_handle* h, const int32_t* ids_host, const int32_t* eos_pos_host, int32_t P, float* text_emb_out_dev, void* stream);
 
 /* Replaces: HumanML3DDataModule.feats2joints (mld/data/HumanML3D.py:41-45 -> recover_from_ric,
  * mld/data/humanml/scripts/motion_process.py:415-432).  feats [B,T,nfeats] -> joints [B,T,njoints,3]. */

@@ -116,6 +116,15 @@ const char* config_error(const mldhip_config* cfg) {
   if (cfg->precision == 3) return "precision 3 (MLDHIP_PREC_FP8_DENOISER of ABI <= 4) was retired in ABI 5: it met no tolerance and was slower than MLDHIP_PREC_F16X3 (include/mldhip.h)";
   if (cfg->precision < MLDHIP_PREC_F32 || cfg->precision > MLDHIP_PREC_BF16) return "unsupported precision";
   if (cfg->max_in_flight < 1 || cfg->max_in_flight > 8) return "max_in_flight must be 1..8";
+  if (cfg->clip_layers < 0 || cfg->clip_layers > 48) return "clip_layers must be 0 (no text tower) .. 48";
+  if (cfg->clip_layers > 0) {      // the CLIP text tower (mldhip_text_encode)
+    if (cfg->clip_heads < 1 || cfg->clip_ff < 1 || cfg->clip_vocab < 1 || cfg->clip_ctx < 1 || cfg->clip_max_prompts < 1) return "text tower: clip_heads, clip_ff, clip_vocab, clip_ctx and clip_max_prompts must be positive";
+    if (cfg->text_dim % cfg->clip_heads || cfg->text_dim / cfg->clip_heads != 64) return "text tower: text_dim / clip_heads must be 64 (head dim of the attention kernel)";
+    if (cfg->clip_ctx > 80) return "text tower: clip_ctx must be <= 80 (five key tiles of 16)";
+    if (cfg->text_dim != 768 || cfg->clip_ff != 3072) return "text tower: the GEMMs are built for text_dim 768 and clip_ff 3072 (CLIP ViT-L/14)";
+    if (cfg->precision == MLDHIP_PREC_BF16) return "text tower: MLDHIP_PREC_BF16 is refused (exact fp32 or split-f16 only)";
+    if ((long long)cfg->clip_max_prompts * cfg->clip_ctx > (1 << 20)) return "text tower: clip_max_prompts x clip_ctx must be <= 2^20 rows";
+  }
   return nullptr;
 }
 
@@ -182,6 +191,16 @@ void carve_latent(E* e, Carver& want) {
   want(&e->text_in, 2 * Bm * TD); want(&e->lat_in, Bm * D);
 }
 
+// workspace of the CLIP text tower (engine/path_clip.hpp), carved only when clip_layers > 0: sized for clip_max_prompts x clip_ctx token rows
+void carve_clip(E* e, Carver& want) {
+  const auto& c = e->cfg;
+  if (c.clip_layers <= 0) return;
+  const size_t Pm = (size_t)c.clip_max_prompts, R = Pm * (size_t)c.clip_ctx, W = (size_t)c.text_dim, F = (size_t)c.clip_ff;
+  want(&e->cX, R * W); want(&e->cLN, R * W); want(&e->cQKV, R * 3 * W); want(&e->cAO, R * W); want(&e->cFF, R * F);
+  want(&e->cE0, Pm * W); want(&e->cE1, Pm * W);
+  want(&e->cTab, 2 * R + 4 * Pm);      // ints: token id and position per row; row offset, row count and EOS row per unique prompt; unique index per prompt
+}
+
 // Kernels launched with more dynamic LDS than the default limit register their size once per process and device (tests/test_cabi.py compares this list
 // with the MLD_LAUNCH sites of engine/*.hpp)
 void register_dynamic_lds() {
@@ -224,6 +243,8 @@ void register_dynamic_lds() {
   (void)hipFuncSetAttribute((const void*)cross2_fold_ln_kernel<512, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, kC2LdsBytes);
   (void)hipFuncSetAttribute((const void*)cross_fold_kernel<512, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, kCrossFoldLdsBytes);
   (void)hipFuncSetAttribute((const void*)attn_decode_x3_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, attn_x3_lds_bytes<4>());
+  (void)hipFuncSetAttribute((const void*)clip_attn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kClipAttnLdsBytes);
+  (void)hipFuncSetAttribute((const void*)clip_attn_x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kClipAttnX3LdsBytes);
   (void)hipFuncSetAttribute((const void*)gemm_pipe_x3_kernel<2, 4, 4, 4, 16, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (gemm_pipe_lds_bytes<2, 4, 4, 4>()));
   (void)hipFuncSetAttribute((const void*)gemm_pipe_x3_kernel<2, 4, 4, 4, 32, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (gemm_pipe_lds_bytes<2, 4, 4, 4>()));
   (void)hipFuncSetAttribute((const void*)den_loop_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLoopLdsBytes);
@@ -333,6 +354,7 @@ int create_engine(const mldhip_config& cfg, int device, int num_cus, mldhip_hand
   Carver want{e};
   if (is_novae(e)) carve_novae(e, want);
   else carve_latent(e, want);
+  carve_clip(e, want);
   const size_t Bm = cfg.max_batch;
   e->ws_floats = want.off;
   e->ctxs.resize(cfg.max_in_flight);

@@ -142,6 +142,25 @@ void gemm_ln(Ctx& c, const GemmArgs& a_) {   // N == 256; full rows per workgrou
   check_launch(c, "gemm_ln");
 }
 
+// The CLIP text tower's GEMMs (engine/path_clip.hpp): K = 768 (in-projection, out-projection, fc1, text_projection) and K = 3072 (fc2) on the
+// staged 64 x 128 tile with the EPI = 1 epilogues (quick-GELU / plain residual add).  ONE tile shape at every row count: a prompt's rows
+// must come out bit-identical whatever else is in the call, so the kernel never depends on M.
+template <int PREC, int KCS>
+void launch_clip_staged(Ctx& c, const GemmArgs& a, dim3 grid) {
+  constexpr int lds = gemm_lds_bytes<2, 4, 2, 2>();
+  MLD_LAUNCH((gemm_kernel<2, 4, 2, 2, false, true, PREC, KCS, false, 1>), grid, dim3(512), lds, c.stream, a);
+}
+void gemm_clip(Ctx& c, const GemmArgs& a_, bool x3) {
+  GemmArgs a = a_;
+  const int K = a.K1;
+  if (x3) use_split_weights(c.e, a, PREC_BF16X3);
+  const dim3 grid((a.M + 63) / 64, (a.N + 127) / 128, 1);
+  if (K == 768) { if (x3) launch_clip_staged<PREC_BF16X3, 24>(c, a, grid); else launch_clip_staged<PREC_F32, 24>(c, a, grid); }
+  else if (K == 3072) { if (x3) launch_clip_staged<PREC_BF16X3, 96>(c, a, grid); else launch_clip_staged<PREC_F32, 96>(c, a, grid); }
+  else c.rc = c.e->fail(MLDHIP_EINVAL, "text tower GEMM: K=%d not in {768, 3072}", K);
+  check_launch(c, "gemm_clip");
+}
+
 GemmArgs lin_args(const float* A, int lda, int K, const float* W, const float* b, float* Y, int ldy, int M, int N) {
   GemmArgs g;
   g.A = A; g.lda = lda; g.K1 = K; g.W = W; g.ldw = K; g.bias = b; g.Y = Y; g.ldy = ldy; g.M = M; g.N = N;

@@ -140,15 +140,44 @@ size_t add_param(E* e, const std::string& key, std::vector<int64_t> shape) {
   p.offset = e->arena_floats;
   const bool enc = key.rfind("vae.encoder.", 0) == 0 || key.rfind("vae.skel_embedding.", 0) == 0 ||
                    key.rfind("vae.global_motion_token", 0) == 0 || key.rfind("vae.query_pos_encoder.", 0) == 0;
-  p.group = key.rfind("denoiser.", 0) == 0 ? 0 : enc ? 3 : key.rfind("vae.", 0) == 0 ? 1 : 2;
+  p.group = key.rfind("denoiser.", 0) == 0 ? 0 : enc ? 3 : key.rfind("vae.", 0) == 0 ? 1 : key.rfind("text_encoder.", 0) == 0 ? 4 : 2;
   e->arena_floats += align_up(p.numel);
   e->index[key] = int(e->params.size());
   e->params.push_back(p);
   return p.offset;
 }
 
+// The CLIP text tower's tensors (clip_layers > 0): transformers' CLIPModel names under the model's text_encoder.text_model.  q | k | v are declared
+// back to back (weights, then biases): each is a multiple of kAlign floats, so together they ARE the packed [3 D][D] in-projection and its [3 D] bias.
+const char* kClipText = "text_encoder.text_model.text_model.";
+std::string clip_layer(int i) { return std::string(kClipText) + "encoder.layers." + std::to_string(i); }
+void declare_clip_params(E* e) {
+  const auto& c = e->cfg;
+  const int64_t W = c.text_dim, F = c.clip_ff;
+  add_param(e, std::string(kClipText) + "embeddings.token_embedding.weight", {(int64_t)c.clip_vocab, W});
+  add_param(e, std::string(kClipText) + "embeddings.position_embedding.weight", {(int64_t)c.clip_ctx, W});
+  for (int i = 0; i < c.clip_layers; ++i) {
+    const std::string p = clip_layer(i);
+    for (const char* n : {"layer_norm1", "layer_norm2"}) { add_param(e, p + "." + n + ".weight", {W}); add_param(e, p + "." + n + ".bias", {W}); }
+    for (const char* n : {"q_proj", "k_proj", "v_proj"}) add_param(e, p + ".self_attn." + n + ".weight", {W, W});
+    for (const char* n : {"q_proj", "k_proj", "v_proj"}) add_param(e, p + ".self_attn." + n + ".bias", {W});
+    add_param(e, p + ".self_attn.out_proj.weight", {W, W});
+    add_param(e, p + ".self_attn.out_proj.bias", {W});
+    add_param(e, p + ".mlp.fc1.weight", {F, W}); add_param(e, p + ".mlp.fc1.bias", {F});
+    add_param(e, p + ".mlp.fc2.weight", {W, F}); add_param(e, p + ".mlp.fc2.bias", {W});
+  }
+  add_param(e, std::string(kClipText) + "final_layer_norm.weight", {W});
+  add_param(e, std::string(kClipText) + "final_layer_norm.bias", {W});
+  add_param(e, "text_encoder.text_model.text_projection.weight", {W, W});
+}
+
 // Declares every tensor the sampling path reads, in execution order.
+void declare_model_params(E* e);
 void declare_params(E* e) {
+  declare_model_params(e);
+  if (e->cfg.clip_layers > 0) declare_clip_params(e);
+}
+void declare_model_params(E* e) {
   const auto& c = e->cfg;
   const int64_t D = c.latent_dim, F = c.ff_size, TD = c.text_dim, NF = c.nfeats;
   const int nb = (c.num_layers - 1) / 2;

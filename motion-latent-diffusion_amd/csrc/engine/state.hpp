@@ -13,7 +13,7 @@ struct Param {
   size_t offset = 0;   // floats into the arena
   size_t numel = 0;
   bool loaded = false;
-  int group = 0;       // 0 denoiser, 1 vae decoder, 2 dataset statistics
+  int group = 0;       // 0 denoiser, 1 vae decoder, 2 dataset statistics, 3 vae encoder, 4 CLIP text tower
 };
 
 struct EncLayerP {   // TransformerEncoderLayer (cross_attention.py:236-272)
@@ -47,6 +47,7 @@ struct WsContext {
   int32_t *lens = nullptr, *lens2 = nullptr, *labels = nullptr;
   NoiseKey* keys = nullptr;            // [max_batch] noise key per motion of the call (stochastic DDIM; uploaded with every call, like lens)
   std::vector<NoiseKey> keys_host;     // stable host copy of what is uploaded to `keys`
+  std::vector<int32_t> clip_tab_host;  // text tower: stable host copy of the call's row / prompt tables (engine/path_clip.hpp)
   bool used = false;
   unsigned long long seed_host = 0;   // stable host copy of the Philox seed while it is uploaded to seed_slot
 #if !defined(MLDHIP_SIM)
@@ -67,7 +68,7 @@ struct mldhip_engine {
   int device = 0;
   std::string err;
   bool finalized = false;
-  bool group_ready[4] = {false, false, false, false};   // denoiser, vae decoder, mean/std, vae encoder
+  bool group_ready[5] = {false, false, false, false, false};   // denoiser, vae decoder, mean/std, vae encoder, CLIP text tower (clip_layers > 0)
 
   // ---- parameters
   std::vector<Param> params;
@@ -128,6 +129,8 @@ struct mldhip_engine {
   float *X0, *Ha, *Hb, *H1, *S[8], *QKV, *AO, *FF, *lat, *T1, *temb0, *tmid, *text_bias, *t1_one, *temb0_one, *time_b2pe;
   // decode
   float *cv1, *cvec, *LNO, *feats_int, *joints_int, *zbuf;
+  // CLIP text tower (clip_layers > 0; engine/path_clip.hpp): packed token rows [clip_max_prompts x clip_ctx][..], EOS rows / embeddings [clip_max_prompts][text_dim], int tables
+  float *cX = nullptr, *cLN = nullptr, *cQKV = nullptr, *cAO = nullptr, *cFF = nullptr, *cE0 = nullptr, *cE1 = nullptr, *cTab = nullptr;
   float* len_rep = nullptr;   // [max_batch] ints: first sample of each sample's length (length_reps_kernel; decoder layer 0 under "dec_lean")
   float* FS = nullptr;   // sample-major loop: parked skip activations [ceil(max_batch / 8)][nb][48][256]
   float *cl_xbuf = nullptr, *cl_park = nullptr, *cl_flags = nullptr;   // cluster loop: exchange regions [clusters][kClXFloats], parked skip rows [workgroups][nb][16][256], flags [clusters][64] + status [16] (words)

@@ -21,7 +21,7 @@
 
 namespace mld {
 
-enum Act : int { ACT_NONE = 0, ACT_GELU = 1, ACT_SILU = 2 };
+enum Act : int { ACT_NONE = 0, ACT_GELU = 1, ACT_SILU = 2, ACT_QGELU = 3 };   // ACT_QGELU: x * sigmoid(1.702 x), CLIP's quick_gelu (EPI = 1 instantiations only)
 
 struct GemmArgs {
   const float* A = nullptr;  int lda = 0;  int K1 = 0;   // first K segment  [M, K1]
@@ -49,20 +49,34 @@ struct Frag { float v[8]; };
 // Copy a [BM][BN] fp32 tile parked in LDS (row stride BN + 4) to Y with 16-byte stores: one wave instruction
 // covers 1 KiB of contiguous output.  (Measured: 32 scattered 4-byte stores per lane -- 64-byte row fragments --
 // cost 13-26 k cycles per workgroup, more than the whole fp32 MFMA main loop; profiles/r01_v8_gemm_phase_trace.)
-template <int BM, int BN, int NT>
-__device__ __forceinline__ void store_tile_from_lds(const float* Cs, float* Y, int ldy, int row0, int col0, int M, int N, int tid) {
+// RES: the tile is added to res[row][col] (row stride ldres) on its way out -- the plain residual add of a pre-LN layer (EPI = 1).
+template <int BM, int BN, int NT, bool RES = false>
+__device__ __forceinline__ void store_tile_from_lds(const float* Cs, float* Y, int ldy, int row0, int col0, int M, int N, int tid,
+                                                    const float* res = nullptr, int ldres = 0) {
   constexpr int CST = BN + 4, V = BN / 4;
-  const bool vec_ok = (ldy & 3) == 0 && col0 + BN <= N && ((reinterpret_cast<unsigned long long>(Y) & 15) == 0);
+  bool vec_ok = (ldy & 3) == 0 && col0 + BN <= N && ((reinterpret_cast<unsigned long long>(Y) & 15) == 0);
+  if constexpr (RES) vec_ok = vec_ok && (ldres & 3) == 0 && ((reinterpret_cast<unsigned long long>(res) & 15) == 0);
   if (vec_ok) {
 #pragma unroll
     for (int j = 0; j < BM * V / NT; ++j) {
       const int idx = tid + j * NT, row = idx / V, c4 = idx - row * V;
-      if (row0 + row < M) st4(Y + (long long)(row0 + row) * ldy + col0 + c4 * 4, ld4(Cs + row * CST + c4 * 4));
+      if (row0 + row < M) {
+        F4 v = ld4(Cs + row * CST + c4 * 4);
+        if constexpr (RES) {
+          const F4 x = ld4(res + (long long)(row0 + row) * ldres + col0 + c4 * 4);
+          v = F4{v.x + x.x, v.y + x.y, v.z + x.z, v.w + x.w};
+        }
+        st4(Y + (long long)(row0 + row) * ldy + col0 + c4 * 4, v);
+      }
     }
   } else {   // ragged right edge / unaligned row stride (final_layer: N = ldy = 263): scalar, still row-contiguous
     for (int idx = tid; idx < BM * BN; idx += NT) {
       const int row = idx / BN, c = idx - row * BN;
-      if (row0 + row < M && col0 + c < N) Y[(long long)(row0 + row) * ldy + col0 + c] = Cs[row * CST + c];
+      if (row0 + row < M && col0 + c < N) {
+        float v = Cs[row * CST + c];
+        if constexpr (RES) v += res[(long long)(row0 + row) * ldres + col0 + c];
+        Y[(long long)(row0 + row) * ldy + col0 + c] = v;
+      }
     }
   }
 }
@@ -115,7 +129,9 @@ constexpr int gemm_lds_bytes() {    // the chunk double buffer, or the output ti
 // KCS (staged path only): K / 32, compile time, so that the whole chunk pipeline is straight-line code: any
 //                 runtime branch around a prefetch load makes hipcc's vmcnt bookkeeping conservative and the
 //                 ring drains at every LDS store (seen in the ISA as vmcnt(5)..vmcnt(0) ladders).
-template <int WM, int WN, int MREP, int NREP, bool LN, bool STAGED = false, int PREC = 0, int KCS = 0, bool TRACE = false>
+// EPI (staged, !LN): 0 = the epilogues above; 1 = the CLIP text tower's (kernels/clip_text.hpp): bias, then quick-GELU (act == ACT_QGELU) or a
+//                 plain residual add (res / ldres, no LayerNorm behind it; Y may be res: every element is read and written by one thread).
+template <int WM, int WN, int MREP, int NREP, bool LN, bool STAGED = false, int PREC = 0, int KCS = 0, bool TRACE = false, int EPI = 0>
 __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs p) {
   static_assert(PREC == PREC_F32 || STAGED, "reduced-precision operands need the LDS-staged main loop");
   constexpr int BM = WM * MREP * 16, BN = WN * NREP * 16;
@@ -430,6 +446,16 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs p) {
           }
       }
     };
+    if constexpr (EPI == 1) {
+      static_assert(STAGED, "the residual epilogue adds while the parked tile is stored");
+      if (p.act == ACT_QGELU) finish([](float x) { return quick_gelu(x); });
+      else finish([](float x) { return x; });
+      __syncthreads();
+      if (p.res) store_tile_from_lds<BM, BN, WM * WN * 64, true>(Cs, Y, p.ldy, blockIdx.x * BM, blockIdx.y * BN, p.M, p.N, tid, p.res, p.ldres);
+      else store_tile_from_lds<BM, BN, WM * WN * 64>(Cs, Y, p.ldy, blockIdx.x * BM, blockIdx.y * BN, p.M, p.N, tid);
+      trace_out();
+      return;
+    }
     if (p.act == ACT_GELU) finish([](float x) { return gelu_erf(x); });
     else if (p.act == ACT_SILU) finish([](float x) { return silu(x); });
     else finish([](float x) { return x; });

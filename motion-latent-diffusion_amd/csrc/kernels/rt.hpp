@@ -237,6 +237,8 @@ __device__ __forceinline__ float gelu_erf(float x) {
   return fmaf(fabsf(h), y, h);
 }
 __device__ __forceinline__ float silu(float x) { return x / (1.0f + expf(-x)); }
+// CLIP's quick_gelu (transformers activations.QuickGELUActivation): x * sigmoid(1.702 x)
+__device__ __forceinline__ float quick_gelu(float x) { return x / (1.0f + expf(-1.702f * x)); }
 
 struct alignas(16) F4 { float x, y, z, w; };
 __device__ __forceinline__ F4 ld4(const float* p) { return *reinterpret_cast<const F4*>(p); }

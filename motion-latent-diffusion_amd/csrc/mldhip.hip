@@ -11,7 +11,7 @@
 //                hipGraph and replayed: the 50-step loop has no host work and no host<->device sync.
 //
 // Source layout: engine/state.hpp (handle, contexts) -> engine/params.hpp (weight contract, schedules) ->
-// engine/dispatch.hpp (kernel selection) -> engine/path_latent.hpp / engine/path_novae.hpp (the model paths) ->
+// engine/dispatch.hpp (kernel selection) -> engine/path_latent.hpp / engine/path_novae.hpp / engine/path_clip.hpp (the model paths, the text tower) ->
 // engine/graphs.hpp (graph capture and caches) -> engine/create.hpp (validation, workspace carve, LDS registration, teardown) ->
 // engine/serve.hpp (the sampling drivers and their shared host sequences) -> engine/probe.hpp (range probe) -> the C ABI below: each
 // entry point is its argument checks and a call into the engine.  kernels/*.hpp hold the device code (no __global__ in this file).
@@ -49,6 +49,7 @@
 #include "kernels/gemm_strip_x3.hpp"
 #include "kernels/final_strip.hpp"
 #include "kernels/dec_half.hpp"
+#include "kernels/clip_text.hpp"
 
 using namespace mld;
 
@@ -57,6 +58,7 @@ using namespace mld;
 #include "engine/dispatch.hpp"
 #include "engine/path_latent.hpp"
 #include "engine/path_novae.hpp"
+#include "engine/path_clip.hpp"
 #include "engine/graphs.hpp"
 #include "engine/create.hpp"
 #include "engine/serve.hpp"
@@ -81,6 +83,8 @@ void mldhip_default_config(mldhip_config* c) {
   c->condition = MLDHIP_COND_TEXT; c->nclasses = 0; c->vae_arch = MLDHIP_VAE_MLD; c->vae_num_layers = 0;
   c->denoiser_arch = MLDHIP_ARCH_TRANS_ENC; c->scheduler_type = MLDHIP_SCHED_DDIM;
   c->max_in_flight = 1;
+  // no text tower by default (clip_layers 0); the other fields are CLIP ViT-L/14's, clip_max_prompts 0 = 2 x max_batch
+  c->clip_layers = 0; c->clip_heads = 12; c->clip_ff = 3072; c->clip_vocab = 49408; c->clip_ctx = 77; c->clip_max_prompts = 0;
 }
 
 const char* mldhip_last_error(mldhip_handle* h) { return h ? h->err.c_str() : g_last_error.c_str(); }
@@ -89,12 +93,15 @@ int mldhip_create(const mldhip_config* cfg, int device, mldhip_handle** out) {
   auto bad = [&](const char* m) { g_last_error = m; return MLDHIP_EINVAL; };
   if (!cfg || !out) return bad("null argument");
   // ABI 6 appended `eta`: a caller built against ABI 5 passes the smaller struct (eta is 0 then); the fields are read from a full-size copy
-  constexpr int32_t kCfgAbi5 = (int32_t)offsetof(mldhip_config, eta);
-  if (cfg->struct_size != (int32_t)sizeof(mldhip_config) && cfg->struct_size != kCfgAbi5) return bad("mldhip_config.struct_size mismatch (ABI skew)");
+  // ABI 7 appended the clip_* fields: a caller built against ABI 6 passes the struct that ends behind eta (no text tower then)
+  constexpr int32_t kCfgAbi5 = (int32_t)offsetof(mldhip_config, eta), kCfgAbi6 = (int32_t)offsetof(mldhip_config, clip_layers);
+  if (cfg->struct_size != (int32_t)sizeof(mldhip_config) && cfg->struct_size != kCfgAbi5 && cfg->struct_size != kCfgAbi6) return bad("mldhip_config.struct_size mismatch (ABI skew)");
   mldhip_config full;
-  std::memset(&full, 0, sizeof full);
-  std::memcpy(&full, cfg, (size_t)cfg->struct_size);
+  mldhip_default_config(&full);                       // fields the caller's struct does not cover keep their defaults ...
+  if (cfg->struct_size == kCfgAbi5) full.eta = 0.0f;
+  std::memcpy(&full, cfg, (size_t)cfg->struct_size);  // ... every field it covers is the caller's
   full.struct_size = (int32_t)sizeof(mldhip_config);
+  if (full.clip_layers > 0 && full.clip_max_prompts == 0) full.clip_max_prompts = 2 * full.max_batch;
   if (const char* what = config_error(&full)) return bad(what);
   int num_cus = 0;
   if (int rc = check_device(device, &num_cus)) return rc;
@@ -258,12 +265,12 @@ int mldhip_finalize_weights(mldhip_handle* e, void* stream_) {
   DeviceGuard dg(e->device);
   // A group (denoiser / vae decoder / mean+std) must be loaded completely or not at all; ops of an
   // absent group fail with MLDHIP_ESTATE, sample() needs all three.
-  int have[4] = {0, 0, 0, 0}, total[4] = {0, 0, 0, 0};
+  int have[5] = {0, 0, 0, 0, 0}, total[5] = {0, 0, 0, 0, 0};
   for (auto& p : e->params) { total[p.group]++; have[p.group] += p.loaded; }
   for (auto& p : e->params)
     if (!p.loaded && have[p.group] != 0) return e->fail(MLDHIP_ENOKEY, "missing tensor %s (strict load)", p.key.c_str());
-  if (have[0] + have[1] + have[2] + have[3] == 0) return e->fail(MLDHIP_ENOKEY, "no tensors loaded");
-  for (int g = 0; g < 4; ++g) e->group_ready[g] = total[g] > 0 && have[g] == total[g];
+  if (have[0] + have[1] + have[2] + have[3] + have[4] == 0) return e->fail(MLDHIP_ENOKEY, "no tensors loaded");
+  for (int g = 0; g < 5; ++g) e->group_ready[g] = total[g] > 0 && have[g] == total[g];
   hipStream_t stream = (hipStream_t)stream_;
   bind_layers(e);
   Ctx c{e, stream};
@@ -525,6 +532,12 @@ int mldhip_ddim_step_eta(mldhip_handle* e, const float* eps_dev, int32_t timeste
   MLD_LAUNCH(ddim_step_eta_kernel, dim3((unsigned)std::min<int64_t>(1024, (n / 4 + 256) / 256)), dim3(256), 0, c.stream, eps_dev, sample_dev,
              noise_dev, prev_dev, (long long)n, ddim_coef(e, timestep), ddim_eta(e, timestep), (unsigned long long)seed, (unsigned)step_index);
   return check_launch(c, "ddim_step_eta");
+}
+
+int mldhip_text_encode(mldhip_handle* e, const int32_t* ids_host, const int32_t* eos_pos_host, int32_t P, float* text_emb_out_dev, void* stream_) {
+  if (!e) return MLDHIP_EINVAL;
+  DeviceGuard dg(e->device);
+  return text_encode_impl(e, ids_host, eos_pos_host, P, text_emb_out_dev, (hipStream_t)stream_);
 }
 
 int mldhip_feats2joints(mldhip_handle* e, const float* feats_dev, int32_t B, int32_t T, float* joints_out_dev, void* stream_) {

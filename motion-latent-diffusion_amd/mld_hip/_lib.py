@@ -14,7 +14,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(_HERE, "libmldhip.so")
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 
 class MldHipError(RuntimeError):
@@ -35,6 +35,8 @@ class Config(C.Structure):
         ("condition", C.c_int32), ("nclasses", C.c_int32), ("vae_arch", C.c_int32), ("vae_num_layers", C.c_int32),
         ("denoiser_arch", C.c_int32), ("scheduler_type", C.c_int32), ("max_in_flight", C.c_int32),
         ("eta", C.c_float),
+        ("clip_layers", C.c_int32), ("clip_heads", C.c_int32), ("clip_ff", C.c_int32), ("clip_vocab", C.c_int32),
+        ("clip_ctx", C.c_int32), ("clip_max_prompts", C.c_int32),
     ]
 
 
@@ -98,6 +100,7 @@ _SYMBOLS = {
     "mldhip_ddim_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "mldhip_ddim_step_eta": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p,
                                        C.c_int64, C.c_void_p]),
+    "mldhip_text_encode": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_void_p]),
     "mldhip_feats2joints": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "mldhip_get_timesteps": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]),
     "mldhip_get_alphas_cumprod": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int32]),
@@ -328,6 +331,16 @@ class Engine:
         """DDIMScheduler.step with the handle's eta (mldhip_ddim_step_eta): ``noise`` [n] injected, or None for the Philox stream (seed, step_index)."""
         self._check(self.lib.mldhip_ddim_step_eta(self._h, _ptr(eps), int(timestep), _ptr(sample), _ptr(noise), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                                   int(step_index), _ptr(prev_sample), n, stream))
+
+    def text_encode(self, ids, eos_pos, out, stream: int = 0):
+        """The CLIP text tower (mldhip_text_encode; engines created with clip_layers > 0): ``ids`` [P, clip_ctx] token ids and ``eos_pos`` [P] on the
+        host, ``out`` [P, 1, text_dim] on the device."""
+        ids = np.ascontiguousarray(np.asarray(ids), dtype=np.int32)
+        eos = np.ascontiguousarray(np.asarray(eos_pos), dtype=np.int32).reshape(-1)
+        if ids.ndim != 2 or ids.shape[0] != eos.shape[0] or (ids.shape[0] and ids.shape[1] != self.cfg.clip_ctx):
+            raise ValueError(f"ids must be [P, {self.cfg.clip_ctx}] with one eos_pos per row, got {ids.shape} / {eos.shape}")
+        self._check(self.lib.mldhip_text_encode(self._h, ids.ctypes.data_as(C.POINTER(C.c_int32)), eos.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                int(ids.shape[0]), _ptr(out), stream))
 
     def feats2joints(self, feats, B: int, T: int, joints_out, stream: int = 0):
         self._check(self.lib.mldhip_feats2joints(self._h, _ptr(feats), B, T, _ptr(joints_out), stream))

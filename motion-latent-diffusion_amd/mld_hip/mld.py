@@ -57,13 +57,13 @@ class MLD(nn.Module):
         self.vae = instantiate_from_config(cfg.model.motion_vae) if self.vae_type != "no" else None      # mld.py:58-59
         self.denoiser = instantiate_from_config(cfg.model.denoiser)
         self.scheduler = instantiate_from_config(cfg.model.scheduler)
-        for m in (self.vae, self.denoiser):
+        for m in (self.vae, self.denoiser, self.text_encoder):
             if engine_key is not None and m is not None and hasattr(m, "use_engine"):
                 m.use_engine(engine_key)
         # ONE engine for all parts of this model: every part asks the registry for the union of the architecture fields
         # (the fused sample() needs every weight group in one handle); another model with other fields gets its own engine
         shared = {}
-        for m in (self.denoiser, self.vae):
+        for m in (self.denoiser, self.vae, self.text_encoder):      # (a HipMldTextEncoder adds the tower's fields: its weights live in the same handle)
             shared.update(getattr(m, "_arch", {}) or {})
         if hasattr(self.scheduler, "engine_config"):
             shared.update(self.scheduler.engine_config(cfg.model.scheduler.num_inference_timesteps))
@@ -75,9 +75,11 @@ class MLD(nn.Module):
             self.eta = 0.0
         if self.vae_type != "no":
             shared["eta"] = self.eta
-        for m in (self.denoiser, self.vae, datamodule, self.scheduler):
+        for m in (self.denoiser, self.vae, datamodule, self.scheduler, self.text_encoder):
             if m is not None and hasattr(m, "_shared_arch") and engine_key is None:
                 m._shared_arch = shared
+        if hasattr(self.text_encoder, "_shared_arch"):
+            self.text_encoder._variant = self.variant
         if hasattr(self.scheduler, "_variant"):
             self.scheduler._variant = self.variant
         self.sample_mean = False
