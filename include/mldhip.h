@@ -34,7 +34,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define MLDHIP_ABI_VERSION 7
+#define MLDHIP_ABI_VERSION 8
 
 enum {
   MLDHIP_OK = 0,
@@ -270,7 +270,7 @@ int mldhip_finalize_weights(mldhip_handle* h, void* stream);
  *                     to drive the LDS-staged kernels at simulator-sized shapes) */
 int mldhip_set_option(mldhip_handle* h, const char* name, int64_t value);
 
-/* Range contract of MLDHIP_PREC_F16X3 (ABI 4; ABI 5 adds the decoder's half Q | K | V form).  A split operand x = hi + lo keeps 22 mantissa bits only while x sits inside the
+/* Range contract of MLDHIP_PREC_F16X3 (ABI 4; ABI 5 adds the decoder's half Q | K | V form, ABI 8 the text tower's stage).  A split operand x = hi + lo keeps 22 mantissa bits only while x sits inside the
  * half format's comfortable range: |x| > 65 504 has no high half (operands produced inside a kernel -- LayerNorm / GELU /
  * attention outputs -- are not clamped: they become inf, then NaN; weights and caller inputs saturate), and the low half of
  * |x| < 2^-3 is a half subnormal (absolute error <= 3e-8 -- harmless for an O(1) tensor, NOT for one that lives at 1e-4: a
@@ -306,6 +306,18 @@ int mldhip_set_option(mldhip_handle* h, const char* name, int64_t value);
  * the half form exists for weights that pass the probe: same 4 x 64 frames on UNIT-normal latents, against the exact-fp32 decode of the same latents,
  * bound MLDHIP_PROBE_TOL_HALF = 3e-5 (a decode error of e ends ~ 7.5 e x max|feats| on the joints: 2.5e-4 at most); above it, or with the option
  * off, the block runs on fp32 Q | K | V and x3 products (decode_half_ok = 0).
+ * ABI 8: the CLIP text tower (mldhip_text_encode) is a fourth stage.  PROBE: when the handle is F16X3, carries a tower (clip_layers > 0) and its weight group
+ * is loaded, finalize encodes four seeded prompts (ids drawn mod clip_vocab; 2, 17, 33 and clip_ctx token rows) on the split-f16 tower and on the exact-fp32
+ * tower of the same handle: probe_err_text = max|split - fp32| / max|fp32| over the four embeddings.  FALLBACK: above MLDHIP_PROBE_TOL (or not finite)
+ * text_split_ok = 0 and every mldhip_text_encode runs the fp32 GEMMs and attention: results equal MLDHIP_PREC_F32's to the bit.  RUN TIME: the rows the tower's
+ * GEMMs read are all produced by its own kernels and are split without a range clamp, so with the probe off a hidden activation beyond 65 504 ends as NaN
+ * embeddings in the non-finite counter, not as a saturated finite row.  Readings (two random-init layers at the real widths, MI355X,
+ * tests/test_gpu_text_tower_rows.py -> profiles/text_tower_rows.json; every row of the tower against transformers in float64, in units of e32 = the float32-CPU
+ * error of the same model): plain weights read 2.3e-6 and stay split (worst row 3.4 x e32); q / k x 4 4.4e-6 (2.0 x), the same with an attention sink on key 0
+ * 3.9e-6 (2.5 x), outlier embedding channels 1.0e-6 (1.5 x), fc1 x 8 / x 32 2.7e-6 / 2.4e-6 (3.7 x / 2.7 x): all stay split.  fc1 x 64 with fc2 x 1/64 -- the
+ * small-weights limit above: fc2's weights sit at 3e-4, where the low half is a subnormal -- reads 6.1e-5 (4.4e-5 on the one-layer simulator tower, where plain
+ * reads 2.8e-6) and falls back; left split it ends 63 x e32 from fp64 with finite outputs and a silent counter.  fc1 x 2^16 (hidden activation 2.4e5) reads inf and
+ * falls back; with "range_probe" 0 it returns NaN rows, all of them counted.
  * The other modes: F32 has no such limits; BF16 is a reported-only mode whose errors bench.py prints. */
 #define MLDHIP_PROBE_TOL 6e-6f
 #define MLDHIP_PROBE_TOL_HALF 3e-5f
@@ -323,6 +335,9 @@ typedef struct mldhip_numeric_info {
                                  2 left after a launch ran into its wait bound (the next sample call already runs on the other loop families; "loop_kernel" 4 re-arms it),
                                  3 another PROCESS holds this device's cluster lane (/tmp/mldhip_cluster_lane_<pci bus id>.lock): never launched by this process */
   int32_t reserved;
+  /* ---- ABI 8: the CLIP text tower's stage.  Written only when struct_size covers them (an ABI-7 caller's smaller struct is accepted and gets the fields above). */
+  int32_t text_split_ok;      /* 1: mldhip_text_encode multiplies on split-f16 MFMAs; 0: fell back to exact fp32, or no tower / another mode */
+  float probe_err_text;       /* the tower stage's err (-1: not probed / no tower) */
 } mldhip_numeric_info;
 /* Synchronises the device (it reads the counter), fills *out and resets nonfinite_values.  No reference counterpart. */
 int mldhip_numeric_status(mldhip_handle* h, mldhip_numeric_info* out);
@@ -477,7 +492,7 @@ int mldhip_ddim_step_eta(mldhip_handle* h, const float* eps_dev, int32_t timeste
  *      and stored to every duplicate's output row (deduplicated on the host, on the id rows);
  *   3. the last stage: final_layer_norm and the projection run on the EOS rows only.
  * A prompt's output row is bit-identical whatever else is in the call.  Arithmetic: the handle's mode (MLDHIP_PREC_F32 exact-fp32 MFMAs,
- * MLDHIP_PREC_F16X3 split-f16 GEMMs and attention products; fp32 LayerNorm, softmax, residuals).  Issued eagerly (no hipGraph: the row total changes
+ * MLDHIP_PREC_F16X3 split-f16 GEMMs and attention products -- unless finalize's range probe moved the tower to fp32: "Range contract", text_split_ok; fp32 LayerNorm, softmax, residuals).  Issued eagerly (no hipGraph: the row total changes
  * per call), stream-ordered like every other call; non-finite output values are counted into mldhip_numeric_status like latents and joints.
  * Returns MLDHIP_EINVAL for P > clip_max_prompts, an id outside [0, clip_vocab) or eos_pos outside [0, clip_ctx); MLDHIP_ESTATE when the handle has no
  * tower (clip_layers = 0), the tower's weight group is absent, or the handle is not finalized. */

@@ -26,7 +26,8 @@ ClipLayerP bind_clip_layer(E* e, int i) {
   return L;
 }
 
-int text_encode_impl(E* e, const int32_t* ids_host, const int32_t* eos_host, int NP, float* out_dev, hipStream_t stream) {
+// count: the call's non-finite output values go into the handle's sticky counter (the range probe's own calls do not: engine/probe.hpp)
+int text_encode_impl(E* e, const int32_t* ids_host, const int32_t* eos_host, int NP, float* out_dev, hipStream_t stream, bool count = true) {
   const auto& cfg = e->cfg;
   if (cfg.clip_layers <= 0) return e->fail(MLDHIP_ESTATE, "mldhip_text_encode: the handle was created without a text tower (mldhip_config.clip_layers = 0)");
   if (!e->finalized || !e->group_ready[4]) return e->fail(MLDHIP_ESTATE, "mldhip_text_encode before finalize / text_encoder.* tower tensors not loaded");
@@ -68,7 +69,7 @@ int text_encode_impl(E* e, const int32_t* ids_host, const int32_t* eos_host, int
   const int32_t *d_tok = dtab, *d_pos = d_tok + R, *d_off = d_pos + R, *d_cnt = d_off + U, *d_eos = d_cnt + U, *d_dup = d_eos + U;
 
   Ctx c{e, stream};
-  const bool x3 = cfg.precision == MLDHIP_PREC_F16X3 && e->arena_x3;
+  const bool x3 = cfg.precision == MLDHIP_PREC_F16X3 && e->arena_x3 && e->text_split_ok;      // text_split_ok: finalize's range probe
   const unsigned ew = (unsigned)std::min<long long>(2048, ((long long)R * W / 4 + 255) / 256);
   MLD_LAUNCH(clip_embed_kernel, dim3(ew), dim3(256), 0, stream, P(e, std::string(kClipText) + "embeddings.token_embedding.weight"),
              P(e, std::string(kClipText) + "embeddings.position_embedding.weight"), d_tok, d_pos, e->cX, R, W);
@@ -101,7 +102,7 @@ int text_encode_impl(E* e, const int32_t* ids_host, const int32_t* eos_host, int
   gemm_clip(c, lin_args(e->cE0, W, W, P(e, "text_encoder.text_model.text_projection.weight"), nullptr, e->cE1, W, U, W), x3);
   if (c.rc) return c.rc;
   MLD_LAUNCH(clip_scatter_kernel, dim3((unsigned)std::min(1024, (NP * W / 4 + 255) / 256)), dim3(256), 0, stream, e->cE1, d_dup, out_dev, NP, W);
-  check_launch(c, "clip_scatter");
+  if (check_launch(c, "clip_scatter") || !count) return c.rc;
   MLD_LAUNCH(count_nonfinite_kernel, dim3((unsigned)std::min(256, (NP * W + 255) / 256)), dim3(256), 0, stream, out_dev, (long long)NP * W, e->nonfinite);
   return check_launch(c, "count_nonfinite");
 }

@@ -1,6 +1,6 @@
 // Range probe of the F16X3 mode (include/mldhip.h "Range contract"): the split-f16 kernels against the exact-fp32 ones of the SAME
-// handle on one seeded probe batch; a stage that disagrees (or is not finite) is switched to the fp32 kernels.  Three stages -- the reverse
-// loop, the decoder, the diffusion-only denoiser -- over one seeded generator and the helpers at the top.
+// handle on one seeded probe batch; a stage that disagrees (or is not finite) is switched to the fp32 kernels.  Four stages -- the reverse
+// loop, the decoder, the diffusion-only denoiser, the CLIP text tower -- over one seeded generator and the helpers at the top.
 // Part of libmldhip's single translation unit (included by ../mldhip.hip, in this order: state, params, dispatch,
 // path_latent, path_novae, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace).
 #pragma once
@@ -30,6 +30,7 @@ struct ProbeLift {
 
 struct ProbeRng {      // Box-Muller, seeded: the probe is a function of the weights only
   unsigned long long st = 0x9E3779B97F4A7C15ull;
+  unsigned bits() { st = st * 6364136223846793005ull + 1442695040888963407ull; return (unsigned)(st >> 40); }      // 24 bits
   float uni() { st = st * 6364136223846793005ull + 1442695040888963407ull; return (float)((st >> 40) + 1) * (1.0f / 16777217.0f); }
   void fill(std::vector<float>& v, float scale) {
     for (size_t i = 0; i + 1 < v.size(); i += 2) {
@@ -289,6 +290,30 @@ int probe_novae(E* e, hipStream_t stream, ProbeRng& rng) {
   return MLDHIP_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- stage 4: the CLIP text tower
+// one mldhip_text_encode of four seeded prompts (2, 17, 33 and clip_ctx token rows: a short prompt, both sides of the x3 attention's 32-key
+// block edge, the full context) on the split-f16 tower and on the exact-fp32 tower of the same handle.  The tower picks its kernels by the
+// arithmetic alone (one GEMM tile and one attention kernel per mode at every row count, engine/dispatch.hpp gemm_clip): nothing to lift.
+int probe_text(E* e, hipStream_t stream, ProbeRng& rng) {
+  const int ctx = e->cfg.clip_ctx, W = e->cfg.text_dim;
+  const int lens[4] = {2, 17, 33, ctx};
+  const int NP = std::min(4, e->cfg.clip_max_prompts);
+  std::vector<int32_t> ids((size_t)NP * ctx), eos(NP);
+  for (auto& id : ids) id = (int32_t)(rng.bits() % (unsigned)e->cfg.clip_vocab);
+  for (int p = 0; p < NP; ++p) eos[p] = std::min(lens[4 - NP + p], ctx) - 1;      // (fewer than 4 prompts of capacity: the longest ones)
+  ProbeDev out;
+  if (out.make((size_t)NP * W)) return e->fail(MLDHIP_EHIP, "range probe: hipMalloc");
+  std::vector<float> ha, hb;
+  for (int split = 1; split >= 0; --split) {
+    e->text_split_ok = split != 0;
+    if (int rc = text_encode_impl(e, ids.data(), eos.data(), NP, out.p, stream, false)) return rc;
+    if (int rc = probe_down(e, stream, out.p, (size_t)NP * W, split ? ha : hb)) return rc;
+  }
+  e->probe_err_text = rel_err(ha, hb);
+  e->text_split_ok = e->probe_err_text <= MLDHIP_PROBE_TOL;
+  return MLDHIP_OK;
+}
+
 int range_probe(E* e, hipStream_t stream, const float* user_text, const float* user_lat, int user_B) {
   Scoped<bool> noise_off(e->noise_off, true);      // deterministic on every handle: the probe compares arithmetic on the eta = 0 step (include/mldhip.h "range_probe")
   ProbeRng rng;
@@ -300,6 +325,8 @@ int range_probe(E* e, hipStream_t stream, const float* user_text, const float* u
     if (int rc = probe_decoder(e, stream, rng)) return rc;
   if (e->group_ready[0] && is_novae(e))
     if (int rc = probe_novae(e, stream, rng)) return rc;
+  if (e->cfg.clip_layers > 0 && e->group_ready[4] && e->arena_x3)
+    if (int rc = probe_text(e, stream, rng)) return rc;
   e->phase = 0;
   return MLDHIP_OK;
 }

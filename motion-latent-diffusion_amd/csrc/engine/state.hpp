@@ -180,6 +180,8 @@ struct mldhip_engine {
   bool split_decode_ok = true;   // false: decoder / encoder / diffusion-only GEMMs and attention run on exact-fp32 MFMAs
   bool dec_half_ok = true;       // false: the probe read the half-Q|K|V form of the decoder's self-attention block above MLDHIP_PROBE_TOL_HALF: the decoder keeps fp32 Q | K | V and x3 products
   float probe_err_decode_half = -1.f;
+  bool text_split_ok = true;     // false: the CLIP text tower (engine/path_clip.hpp) runs its GEMMs and attention on exact-fp32 MFMAs
+  float probe_err_text = -1.f;   // the tower stage's reading (-1: not probed / no tower)
   float probe_err_loop = -1.f, probe_err_decode = -1.f;   // probe results (max-abs difference / max-abs reference); -1: not probed
   unsigned* nonfinite = nullptr; // device counter: non-finite values seen in the latents / joints a sample call produced (sticky until read)
 

@@ -256,8 +256,15 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs p) {
           // row image: [32 x bf16 hi | 32 x bf16 lo | pad]; this thread owns k = 4*c4 .. 4*c4+3
           if (p.w_split && j >= NLA) { st4(dst + row * kGemmLdsStride + c4 * 4, v); continue; }   // W was split at finalize (split_bf16_weights_kernel): already the row image
           unsigned h0, l0, h1, l1;
-          split16_pair(v.x, v.y, h0, l0);
-          split16_pair(v.z, v.w, h1, l1);
+          if (EPI == 1 && j < NLA) {
+            // the text tower's A rows are all produced inside its own kernels (LayerNorm, attention, quick-GELU outputs): no range clamp, so that a hidden
+            // activation beyond +-65 504 ends as NaN in the output and in the non-finite counter instead of a saturated, finite, wrong row (mldhip.h "Range contract" 3)
+            split16_two(v.x, v.y, h0, l0);
+            split16_two(v.z, v.w, h1, l1);
+          } else {
+            split16_pair(v.x, v.y, h0, l0);
+            split16_pair(v.z, v.w, h1, l1);
+          }
           unsigned* rowp = reinterpret_cast<unsigned*>(dst + row * kGemmLdsStride);
           *reinterpret_cast<uint2_t*>(rowp + c4 * 2) = uint2_t{h0, h1};
           *reinterpret_cast<uint2_t*>(rowp + 16 + c4 * 2) = uint2_t{l0, l1};

@@ -328,8 +328,8 @@ int mldhip_finalize_weights(mldhip_handle* e, void* stream_) {
   if (e->loop_kernel == 3 && !e->loop_ips)      // (set before finalize: refused here, like mldhip_set_option refuses it afterwards)
     return e->fail(MLDHIP_EINVAL, "loop_kernel 3: the sample-major loop is built for fp32 / split-f16 loop arithmetic, latent_dim 256, ff_size 1024, 4 heads");
   e->finalized = true;
-  e->split_loop_ok = e->split_decode_ok = e->dec_half_ok = true;
-  e->probe_err_loop = e->probe_err_decode = e->probe_err_decode_half = -1.f;
+  e->split_loop_ok = e->split_decode_ok = e->dec_half_ok = e->text_split_ok = true;
+  e->probe_err_loop = e->probe_err_decode = e->probe_err_decode_half = e->probe_err_text = -1.f;
   if (e->cfg.precision == MLDHIP_PREC_BF16X3_DECODE && e->range_probe) {
     if (int rc = range_probe(e, stream)) { e->finalized = false; return rc; }
     e->probe_first_call = e->range_probe == 2;
@@ -339,7 +339,9 @@ int mldhip_finalize_weights(mldhip_handle* e, void* stream_) {
 
 int mldhip_numeric_status(mldhip_handle* e, mldhip_numeric_info* out) {
   if (!e || !out) return MLDHIP_EINVAL;
-  if (out->struct_size != (int32_t)sizeof(mldhip_numeric_info)) return e->fail(MLDHIP_EINVAL, "mldhip_numeric_info.struct_size mismatch (ABI)");
+  // ABI 8 appended the text tower's two fields: a caller built against ABI 7 passes the struct that ends behind `reserved` and gets the fields it knows
+  constexpr int32_t kInfoAbi7 = (int32_t)offsetof(mldhip_numeric_info, text_split_ok);
+  if (out->struct_size != (int32_t)sizeof(mldhip_numeric_info) && out->struct_size != kInfoAbi7) return e->fail(MLDHIP_EINVAL, "mldhip_numeric_info.struct_size mismatch (ABI)");
   DeviceGuard dg(e->device);
   HIP_TRY(e, hipDeviceSynchronize());
   unsigned n = 0;
@@ -348,7 +350,7 @@ int mldhip_numeric_status(mldhip_handle* e, mldhip_numeric_info* out) {
   // a cluster launch that ran into its wait bound poisoned its latents (counted above) and left its status word set: the handle stays off the cluster loop from here on
   // (the captured graphs that hold it are dropped); mldhip_set_option("loop_kernel", 4) re-arms it
   if (!e->cluster_failed && cluster_timed_out(e)) leave_cluster_loop(e);
-  out->probed = e->probe_err_loop >= 0.f || e->probe_err_decode >= 0.f;
+  out->probed = e->probe_err_loop >= 0.f || e->probe_err_decode >= 0.f || e->probe_err_text >= 0.f;
   out->loop_split_ok = e->cfg.precision == MLDHIP_PREC_BF16X3_DECODE && e->split_loop_ok;
   out->decode_split_ok = e->cfg.precision == MLDHIP_PREC_BF16X3_DECODE && e->split_decode_ok;
   out->probe_err_loop = e->probe_err_loop;
@@ -358,6 +360,10 @@ int mldhip_numeric_status(mldhip_handle* e, mldhip_numeric_info* out) {
   out->reserved = 0;
   out->decode_half_ok = e->cfg.precision == MLDHIP_PREC_BF16X3_DECODE && e->split_decode_ok && e->dec_half && (e->dec_half_ok || e->dec_half == 2);
   out->probe_err_decode_half = e->probe_err_decode_half;
+  if (out->struct_size > kInfoAbi7) {
+    out->text_split_ok = e->cfg.clip_layers > 0 && e->cfg.precision == MLDHIP_PREC_F16X3 && e->arena_x3 && e->text_split_ok;
+    out->probe_err_text = e->probe_err_text;
+  }
   return MLDHIP_OK;
 }
 

@@ -14,7 +14,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(_HERE, "libmldhip.so")
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 
 class MldHipError(RuntimeError):
@@ -56,7 +56,8 @@ class NumericInfo(C.Structure):
     """Mirror of ``mldhip_numeric_info`` (include/mldhip.h, "Range contract" of the split-f16 mode)."""
     _fields_ = [("struct_size", C.c_int32), ("probed", C.c_int32), ("loop_split_ok", C.c_int32), ("decode_split_ok", C.c_int32),
                 ("probe_err_loop", C.c_float), ("probe_err_decode", C.c_float), ("nonfinite_values", C.c_int64),
-                ("decode_half_ok", C.c_int32), ("probe_err_decode_half", C.c_float), ("cluster_loop", C.c_int32), ("reserved", C.c_int32)]
+                ("decode_half_ok", C.c_int32), ("probe_err_decode_half", C.c_float), ("cluster_loop", C.c_int32), ("reserved", C.c_int32),
+                ("text_split_ok", C.c_int32), ("probe_err_text", C.c_float)]
 
 
 PROBE_TOL = 6e-6                         # MLDHIP_PROBE_TOL

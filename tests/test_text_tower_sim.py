@@ -1,6 +1,8 @@
 """The CLIP text tower of the engine (mldhip_text_encode, ABI 7) on the functional simulator: one layer, P = 3 prompts with EOS at
 1, 17 and 20 (about 40 token rows), against transformers' own CLIPTextModelWithProjection in float64 (tests/clip_tower_ref.py has the
-reference and the tolerance rule), plus the causality / duplicate rules and the ABI checks that need no device."""
+reference and the tolerance rule), plus the causality / duplicate rules and the ABI checks that need no device.  The second half looks at
+token rows instead of EOS rows (clip_tower_ref.reference_rows: the prefixes of one id row return every row of the tower), at a second weight
+regime and at the tower's stage of the range contract."""
 import ctypes as C
 
 import numpy as np
@@ -81,7 +83,7 @@ def test_duplicates_and_batch_independence(engines, ids, outputs):
 
 def test_abi_7_config_and_guards(engines, ids):
     lib = simlib.sim_library()
-    assert lib.mldhip_abi_version() == 7 == _lib.ABI_VERSION
+    assert lib.mldhip_abi_version() == 8 == _lib.ABI_VERSION      # (8 appended the tower's fields to mldhip_numeric_info; the config is ABI 7's)
     cfg = _lib.Config()
     lib.mldhip_default_config(C.byref(cfg))
     assert cfg.struct_size == C.sizeof(_lib.Config)
@@ -170,3 +172,84 @@ def test_hip_text_encoder_class_on_the_simulator(tmp_path):
     finally:
         E._engines.pop(key, None)
         eng.close()
+
+
+# ---- every token row, not only EOS rows: prefixes of one id row (tests/test_gpu_text_tower_rows.py is the MI355X counterpart, all 77 rows)
+PREFIXES = [1, 2, 16, 17, 32, 33]          # one row (eos_pos = 0), both sides of a 16-key tile edge and of the x3 form's 32-key P V block edge
+REGIME_ROWS = [1, 17, 33]
+
+
+@pytest.fixture(scope="module")
+def ids_row():
+    return R.make_ids([R.CTX - 1], seed=21)[0]
+
+
+def rows_of(eng, ids_row, lengths):
+    return encode(eng, *R.prefix_call(ids_row, lengths))
+
+
+def check_rows(out, r64, r32, lengths, factor, what):
+    err, e32 = R.row_ratios(out, r64, r32, lengths)
+    print(f"{what}: e32 {e32:.3e}  per-row error / e32 {np.round(err / e32, 2).tolist()} at n = {lengths}")
+    assert e32 > 0 and np.isfinite(out).all()
+    assert (err <= factor * e32).all(), (what, (err / e32).tolist(), factor)
+
+
+def test_prefix_rows_parity_both_modes(engines, ids_row):
+    r64, r32 = R.reference_rows(LAYERS, ids_row)
+    out = {prec: rows_of(engines[prec], ids_row, PREFIXES) for prec in (0, 1)}      # six prompts that differ in length alone: not merged by the dedupe
+    check_rows(out[0], r64, r32, PREFIXES, R.F32_FACTOR, "prefix rows F32")
+    check_rows(out[1], r64, r32, PREFIXES, R.X3_FACTOR, "prefix rows F16X3")
+    again = rows_of(engines[1], ids_row, [33, 1, 17])                                 # other order, other company: the same bits
+    assert np.array_equal(again, out[1][[PREFIXES.index(n) for n in (33, 1, 17)]])
+
+
+def test_sharp_softmax_rows_both_modes(ids_row):
+    """q_proj / k_proj x 4 (logits x 16): rows whose softmax is nearly one-hot, where the max subtraction and the log2-domain exp have work to do"""
+    r64, r32 = R.reference_rows(LAYERS, ids_row, variant="sharp")
+    assert np.isfinite(r32).all() and R.attention_shape(LAYERS, ids_row, variant="sharp")[0] > 0.5
+    for prec, factor in ((0, R.F32_FACTOR), (1, R.X3_FACTOR)):
+        eng = _lib.Engine(lib=simlib.sim_library(), use_graph=0, precision=prec, **R.engine_kwargs(LAYERS, 6))
+        try:
+            assert R.load_tower(eng, LAYERS, variant="sharp") == []
+            check_rows(rows_of(eng, ids_row, REGIME_ROWS), r64, r32, REGIME_ROWS, factor, f"sharp, precision {prec}")
+        finally:
+            eng.close()
+
+
+def test_small_weights_fall_back_to_fp32(ids_row):
+    """fc1 x 64, fc2 x 1/64 (the small-operand limit of the split-f16 format, clip_tower_ref docstring): left on the split kernels the tower ends
+    63 x e32 from fp64 with finite outputs and a silent counter; finalize's probe reads it above MLDHIP_PROBE_TOL, the handle reports the
+    fallback and returns the F32 handle's numbers"""
+    r64, r32 = R.reference_rows(LAYERS, ids_row, variant="small_w")
+    out = {}
+    for prec in (0, 1):
+        eng = _lib.Engine(lib=simlib.sim_library(), use_graph=0, precision=prec, **R.engine_kwargs(LAYERS, 6))
+        try:
+            eng.set_option("range_probe", 1)               # (off by default on the simulator)
+            assert R.load_tower(eng, LAYERS, variant="small_w") == []
+            ns = eng.numeric_status()
+            if prec == 1:
+                print(f"small_w: probe_err_text {ns['probe_err_text']:.3e}")
+                assert ns["probed"] == 1 and ns["text_split_ok"] == 0 and ns["probe_err_text"] > _lib.PROBE_TOL, ns
+            else:
+                assert ns["probed"] == 0 and ns["text_split_ok"] == 0 and ns["probe_err_text"] == -1.0, ns
+            out[prec] = rows_of(eng, ids_row, REGIME_ROWS)
+            assert eng.numeric_status()["nonfinite_values"] == 0
+        finally:
+            eng.close()
+    assert np.array_equal(out[1], out[0])
+    check_rows(out[1], r64, r32, REGIME_ROWS, R.F32_FACTOR, "small_w, F16X3 handle after the fallback")
+
+
+def test_numeric_info_accepts_the_abi_7_struct(engines):
+    """the two tower fields were appended: a caller that passes the shorter struct gets the fields it knows, any other size is refused"""
+    lib = simlib.sim_library()
+    info = _lib.NumericInfo()
+    short = _lib.NumericInfo.text_split_ok.offset
+    C.memset(C.byref(info), 0x55, C.sizeof(info))
+    info.struct_size = short
+    assert lib.mldhip_numeric_status(engines[1]._h, C.byref(info)) == 0
+    assert info.text_split_ok == 0x55555555 and info.loop_split_ok in (0, 1)      # the tail was not written
+    info.struct_size = short - 4
+    assert lib.mldhip_numeric_status(engines[1]._h, C.byref(info)) == EINVAL
