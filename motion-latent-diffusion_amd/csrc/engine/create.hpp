@@ -1,7 +1,7 @@
 // Handle construction and teardown: the cluster-lane lock of a device, config validation, the workspace carve of the two variants,
 // the dynamic-LDS registration list, create_engine / destroy_engine.
 // Part of libmldhip's single translation unit (included by ../mldhip.hip, in this order: state, params, dispatch,
-// path_latent, path_novae, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace).
+// path_loop, streams, path_vae, path_latent, path_novae, path_clip, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace).
 #pragma once
 #if !defined(MLDHIP_SIM)
 #include <fcntl.h>
@@ -268,8 +268,8 @@ void register_dynamic_lds() {
 #define MLD_T32_ATTR(NS)                                                                                                    \
   MLD_T32_ATTR1(32, NS, false, PREC_F32) MLD_T32_ATTR1(32, NS, true, PREC_F32) MLD_T32_ATTR1(16, NS, false, PREC_F32) MLD_T32_ATTR1(16, NS, true, PREC_F32) \
   MLD_T32_ATTR1(32, NS, false, PREC_BF16) MLD_T32_ATTR1(16, NS, false, PREC_BF16)                                             \
-  MLD_T32_ATTR1(32, NS, false, PREC_BF16X3) MLD_T32_ATTR1(16, NS, false, PREC_BF16X3)                                         \
-  MLD_T32_ATTR1(32, NS, true, PREC_BF16X3) MLD_T32_ATTR1(16, NS, true, PREC_BF16X3)
+  MLD_T32_ATTR1(32, NS, false, PREC_F16X3) MLD_T32_ATTR1(16, NS, false, PREC_F16X3)                                         \
+  MLD_T32_ATTR1(32, NS, true, PREC_F16X3) MLD_T32_ATTR1(16, NS, true, PREC_F16X3)
   MLD_T32_ATTR(0) MLD_T32_ATTR(1) MLD_T32_ATTR(2) MLD_T32_ATTR(4)
 #undef MLD_T32_ATTR
 #undef MLD_T32_ATTR1

@@ -1,6 +1,7 @@
 // Launch helpers: which GEMM tile / kernel instance a call maps to.
 // Part of libmldhip's single translation unit (included by ../mldhip.hip, in this order: state, params, dispatch,
-// path_latent, path_novae, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace) except the handle type itself.
+// path_loop, streams, path_vae, path_latent, path_novae, path_clip, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace)
+// except the handle type itself.
 #pragma once
 
 namespace {
@@ -24,11 +25,17 @@ int check_launch(Ctx& c, const char* what) {
   return c.rc;
 }
 
+// One counted launch: MLD_COUNTED(c, "name", <an MLD_LAUNCH of the kernel on c.stream>) is the launch, the launch count of the current phase
+// (mldhip_get_launch_counts) and the error check -- a launch that should count cannot forget to.  A macro around the MLD_LAUNCH text and not a function over the
+// kernel pointer: tests/test_cabi.py reads the MLD_LAUNCH sites of engine/*.hpp against the dynamic-LDS registrations of create.hpp.
+#define MLD_COUNTED(c, what, ...) \
+  do { __VA_ARGS__; count(c); check_launch(c, what); } while (0)
+
 // Tile configurations.  Tiny one-off GEMMs (time MLP, text projection, per-sample cross-attention vectors; M up to
 // e->small_m rows) use the register-direct 16x64 one-tile-per-wave shape; everything else streams both panels through LDS
 // (64x128 tiles on 8 waves, 64x256 with the LayerNorm epilogue; 32x64 on 4 waves for the loop's K = 1024 GEMM at large M).
 
-// staged (LDS, prefetch ring) launch of one tile shape; K / 32 is a template parameter
+// staged (LDS, prefetch ring) launch of one tile shape; K / 32 is a template parameter.  The callers count: one count per GEMM call whichever arm ran
 template <int WM, int WN, int MREP, int NREP, bool LN, int PREC>
 void launch_staged(Ctx& c, const GemmArgs& a, dim3 grid) {
   const int kcs = (a.K1 + a.K2) / 32;
@@ -56,7 +63,7 @@ void launch_staged(Ctx& c, const GemmArgs& a, dim3 grid) {
 int staged_prec(const E* e) {
   const bool big = e->phase == 1 || e->cfg.vae_arch == MLDHIP_VAE_NONE;
   switch (e->cfg.precision) {
-    case MLDHIP_PREC_BF16X3_DECODE: return (big && e->split_decode_ok) ? PREC_BF16X3 : PREC_F32;   // split_decode_ok: finalize's range probe
+    case MLDHIP_PREC_F16X3: return (big && e->split_decode_ok) ? PREC_F16X3 : PREC_F32;   // split_decode_ok: finalize's range probe
     case MLDHIP_PREC_BF16: return PREC_BF16;
     default: return PREC_F32;
   }
@@ -70,16 +77,16 @@ int loop_prec(const E* e) {
 // (option "tile_x3", on by default) -- 24 matrix instructions of 16 cycles per wave instead of 64 of 32, same 22-bit products as the
 // persistent loop of that mode
 int latency_prec(const E* e) {
-  return (e->cfg.precision == MLDHIP_PREC_BF16X3_DECODE && e->tile_x3 && e->split_loop_ok) ? PREC_BF16X3 : loop_prec(e);
+  return (e->cfg.precision == MLDHIP_PREC_F16X3 && e->tile_x3 && e->split_loop_ok) ? PREC_F16X3 : loop_prec(e);
 }
 // ... and the persistent loop (loop_fused.hpp) streams the split-f16 image of its weights
 bool fused_split(const E* e) { return e->loop_stream_x3 && e->fused_x3 && e->split_loop_ok; }
 
-// split-bf16 mode: read W from the pre-split image of the weight arena when it lives there (derived tables in a workspace do not)
+// split-f16 mode: read W from the pre-split image of the weight arena when it lives there (derived tables in a workspace do not)
 void use_split_weights(const E* e, GemmArgs& a, int prec) {
   // the image holds one (hi | lo) record per ALIGNED group of 32 floats of the arena: a weight view that does not start on a
   // group boundary, or whose rows / K slices do not, keeps the in-kernel split
-  if (prec == PREC_BF16X3 && e->arena_x3 && a.W >= e->arena && a.W < e->arena + e->arena_floats &&
+  if (prec == PREC_F16X3 && e->arena_x3 && a.W >= e->arena && a.W < e->arena + e->arena_floats &&
       (a.W - e->arena) % 32 == 0 && a.ldw % 32 == 0 && a.sW % 32 == 0) {
     a.W = e->arena_x3 + (a.W - e->arena);
     a.w_split = 1;
@@ -91,7 +98,7 @@ void use_split_weights(const E* e, GemmArgs& a, int prec) {
 // image, one K segment, N a multiple of the tile width, no per-row masks.  Everything else keeps the 64 x 128 tile.
 bool use_gemm_pipe(const E* e, const GemmArgs& a, int prec, int nz) {
   const int K = a.K1 + a.K2;
-  return e->gemm_pipe && e->cfg.vae_arch == MLDHIP_VAE_NONE && prec == PREC_BF16X3 && a.w_split && nz == 1 && a.K2 == 0 && (K == 512 || K == 1024) &&
+  return e->gemm_pipe && e->cfg.vae_arch == MLDHIP_VAE_NONE && prec == PREC_F16X3 && a.w_split && nz == 1 && a.K2 == 0 && (K == 512 || K == 1024) &&
          a.N % 256 == 0 && (e->gemm_pipe == 2 || a.M >= e->gemm_pipe_min_rows) && !a.lens && !a.skip_lens && !a.relu_in && !e->trace_on && (a.lda & 3) == 0 && (a.ldy & 3) == 0 &&
          ((reinterpret_cast<uintptr_t>(a.A) | reinterpret_cast<uintptr_t>(a.Y) | reinterpret_cast<uintptr_t>(a.bias)) & 15) == 0;   // 16-byte row pieces, bias quads, tile stores
 }
@@ -112,7 +119,7 @@ void gemm(Ctx& c, const GemmArgs& a_, int nz = 1) {
     MLD_LAUNCH((gemm_kernel<1, 4, 1, 1, false>), grid, dim3(256), 0, c.stream, a);
   } else {
     dim3 grid((a.M + 63) / 64, (a.N + 127) / 128, nz);         // 64x128 tile on 8 waves (2 per SIMD)
-    if (prec == PREC_BF16X3) launch_staged<2, 4, 2, 2, false, PREC_BF16X3>(c, a, grid);
+    if (prec == PREC_F16X3) launch_staged<2, 4, 2, 2, false, PREC_F16X3>(c, a, grid);
     else if (prec == PREC_BF16) launch_staged<2, 4, 2, 2, false, PREC_BF16>(c, a, grid);
     else launch_staged<2, 4, 2, 2, false, PREC_F32>(c, a, grid);
   }
@@ -135,7 +142,7 @@ void gemm_ln(Ctx& c, const GemmArgs& a_) {   // N == 256; full rows per workgrou
   const int prec = staged_prec(c.e);
   use_split_weights(c.e, a, prec);
   const dim3 grid((a.M + 63) / 64, 1, 1);
-  if (prec == PREC_BF16X3) launch_staged<2, 4, 2, 4, true, PREC_BF16X3>(c, a, grid);
+  if (prec == PREC_F16X3) launch_staged<2, 4, 2, 4, true, PREC_F16X3>(c, a, grid);
   else if (prec == PREC_BF16) launch_staged<2, 4, 2, 4, true, PREC_BF16>(c, a, grid);
   else launch_staged<2, 4, 2, 4, true, PREC_F32>(c, a, grid);
   count(c);
@@ -153,10 +160,10 @@ void launch_clip_staged(Ctx& c, const GemmArgs& a, dim3 grid) {
 void gemm_clip(Ctx& c, const GemmArgs& a_, bool x3) {
   GemmArgs a = a_;
   const int K = a.K1;
-  if (x3) use_split_weights(c.e, a, PREC_BF16X3);
+  if (x3) use_split_weights(c.e, a, PREC_F16X3);
   const dim3 grid((a.M + 63) / 64, (a.N + 127) / 128, 1);
-  if (K == 768) { if (x3) launch_clip_staged<PREC_BF16X3, 24>(c, a, grid); else launch_clip_staged<PREC_F32, 24>(c, a, grid); }
-  else if (K == 3072) { if (x3) launch_clip_staged<PREC_BF16X3, 96>(c, a, grid); else launch_clip_staged<PREC_F32, 96>(c, a, grid); }
+  if (K == 768) { if (x3) launch_clip_staged<PREC_F16X3, 24>(c, a, grid); else launch_clip_staged<PREC_F32, 24>(c, a, grid); }
+  else if (K == 3072) { if (x3) launch_clip_staged<PREC_F16X3, 96>(c, a, grid); else launch_clip_staged<PREC_F32, 96>(c, a, grid); }
   else c.rc = c.e->fail(MLDHIP_EINVAL, "text tower GEMM: K=%d not in {768, 3072}", K);
   check_launch(c, "gemm_clip");
 }

@@ -1,6 +1,7 @@
 // Diffusion-only path (config 4): trans_dec denoiser on raw motion + DDPM.
 // Part of libmldhip's single translation unit (included by ../mldhip.hip, in this order: state, params, dispatch,
-// path_latent, path_novae, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace) except the handle type itself.
+// path_loop, streams, path_vae, path_latent, path_novae, path_clip, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace)
+// except the handle type itself.
 #pragma once
 
 namespace {
@@ -9,9 +10,7 @@ namespace {
 // Diffusion-only variant (BASELINE config 4): trans_dec denoiser on raw motion, d = 512 (kernels/novae.hpp).
 // Row layout: sample-major rows r*T + t of the CFG batch (r < R = 2B), 512 floats per row.
 void novae_ln(Ctx& c, const float* x, const float* res, const float* g, const float* b, float* y, int M) {
-  MLD_LAUNCH((add_layernorm_rows_kernel<512>), dim3((M + 3) / 4), dim3(256), 0, c.stream, x, res, g, b, y, M);
-  count(c);
-  check_launch(c, "add_layernorm_rows");
+  MLD_COUNTED(c, "add_layernorm_rows", MLD_LAUNCH(add_layernorm_rows_kernel<512>, dim3((M + 3) / 4), dim3(256), 0, c.stream, x, res, g, b, y, M));
 }
 
 void novae_self_attention(Ctx& c, int R, int T, bool force_flash = false) {
@@ -19,33 +18,27 @@ void novae_self_attention(Ctx& c, int R, int T, bool force_flash = false) {
   const int H = e->cfg.num_heads, nkt = pick_nkt(T), nqt = (T + 15) / 16;
   dim3 grid(R * H, (nqt + 7) / 8), block(512);
   const int* nolens = nullptr;    // the reference passes no key-padding mask to the trans_dec denoiser (mld_denoiser.py:215)
-  if (staged_prec(e) == PREC_BF16X3 && T <= 256 && (e->flash_attn == 2 || (e->flash_attn == 1 && (R * H >= 512 || force_flash))) && e->cfg.latent_dim == H * 128) {
+  if (staged_prec(e) == PREC_F16X3 && T <= 256 && (e->flash_attn == 2 || (e->flash_attn == 1 && (R * H >= 512 || force_flash))) && e->cfg.latent_dim == H * 128) {
     // key-blocked form (attention.hpp attn_flash128_x3_kernel): one workgroup per (sample, head), K / V in blocks of 32 keys
-    MLD_LAUNCH(attn_flash128_x3_kernel, dim3(R * H), dim3(512), kFlash128LdsBytes, c.stream, (const float*)e->QKV, e->AO, nolens, T, H);
-    count(c);
-    check_launch(c, "attn_flash128_x3");
+    MLD_COUNTED(c, "attn_flash128_x3", MLD_LAUNCH(attn_flash128_x3_kernel, dim3(R * H), dim3(512), kFlash128LdsBytes, c.stream, e->QKV, e->AO, nolens, T, H));
     return;
   }
-  if (staged_prec(e) != PREC_F32) {   // GEMMs on bf16 MFMAs: the attention runs split-bf16 too
+  if (staged_prec(e) != PREC_F32) {   // GEMMs on 16-bit MFMAs: the attention runs split-f16 too
     switch (nkt) {
-      case 4: MLD_LAUNCH((attn_seq_x3_kernel<4, 128>), grid, block, (attn_seq_x3_lds_bytes<4, 128>()), c.stream, (const float*)e->QKV, e->AO, nolens, T, H); break;
-      case 7: MLD_LAUNCH((attn_seq_x3_kernel<7, 128>), grid, block, (attn_seq_x3_lds_bytes<7, 128>()), c.stream, (const float*)e->QKV, e->AO, nolens, T, H); break;
-      case 13: MLD_LAUNCH((attn_seq_x3_kernel<13, 128>), grid, block, (attn_seq_x3_lds_bytes<13, 128>()), c.stream, (const float*)e->QKV, e->AO, nolens, T, H); break;
-      default: MLD_LAUNCH((attn_seq_x3_kernel<18, 128>), grid, block, (attn_seq_x3_lds_bytes<18, 128>()), c.stream, (const float*)e->QKV, e->AO, nolens, T, H); break;
+      case 4: MLD_COUNTED(c, "attn_seq_x3", MLD_LAUNCH((attn_seq_x3_kernel<4, 128>), grid, block, (attn_seq_x3_lds_bytes<4, 128>()), c.stream, e->QKV, e->AO, nolens, T, H)); break;
+      case 7: MLD_COUNTED(c, "attn_seq_x3", MLD_LAUNCH((attn_seq_x3_kernel<7, 128>), grid, block, (attn_seq_x3_lds_bytes<7, 128>()), c.stream, e->QKV, e->AO, nolens, T, H)); break;
+      case 13: MLD_COUNTED(c, "attn_seq_x3", MLD_LAUNCH((attn_seq_x3_kernel<13, 128>), grid, block, (attn_seq_x3_lds_bytes<13, 128>()), c.stream, e->QKV, e->AO, nolens, T, H)); break;
+      default: MLD_COUNTED(c, "attn_seq_x3", MLD_LAUNCH((attn_seq_x3_kernel<18, 128>), grid, block, (attn_seq_x3_lds_bytes<18, 128>()), c.stream, e->QKV, e->AO, nolens, T, H)); break;
     }
-    count(c);
-    check_launch(c, "attn_seq_x3");
     return;
   }
   const size_t shmem = (size_t)nkt * 16 * 132 * sizeof(float);
   switch (nkt) {
-    case 4: MLD_LAUNCH((attn_seq_kernel<4, 128>), grid, block, shmem, c.stream, (const float*)e->QKV, e->AO, nolens, T, H); break;
-    case 7: MLD_LAUNCH((attn_seq_kernel<7, 128>), grid, block, shmem, c.stream, (const float*)e->QKV, e->AO, nolens, T, H); break;
-    case 13: MLD_LAUNCH((attn_seq_kernel<13, 128>), grid, block, shmem, c.stream, (const float*)e->QKV, e->AO, nolens, T, H); break;
-    default: MLD_LAUNCH((attn_seq_kernel<18, 128>), grid, block, shmem, c.stream, (const float*)e->QKV, e->AO, nolens, T, H); break;
+    case 4: MLD_COUNTED(c, "attn_seq", MLD_LAUNCH((attn_seq_kernel<4, 128>), grid, block, shmem, c.stream, e->QKV, e->AO, nolens, T, H)); break;
+    case 7: MLD_COUNTED(c, "attn_seq", MLD_LAUNCH((attn_seq_kernel<7, 128>), grid, block, shmem, c.stream, e->QKV, e->AO, nolens, T, H)); break;
+    case 13: MLD_COUNTED(c, "attn_seq", MLD_LAUNCH((attn_seq_kernel<13, 128>), grid, block, shmem, c.stream, e->QKV, e->AO, nolens, T, H)); break;
+    default: MLD_COUNTED(c, "attn_seq", MLD_LAUNCH((attn_seq_kernel<18, 128>), grid, block, shmem, c.stream, e->QKV, e->AO, nolens, T, H)); break;
   }
-  count(c);
-  check_launch(c, "attn_seq");
 }
 
 // K|V of the memory tokens for all layers at once (blockIdx.z = layer): dst[l][rows][2D] = src · Wkv_l^T + bkv_l
@@ -62,10 +55,8 @@ void novae_fold_memory(Ctx& c, const float* kv, int ntok, long long kv_layer_str
   E* e = c.e;
   const int D = e->cfg.latent_dim, H = e->cfg.num_heads, L = e->cfg.num_layers;
   if (D != 512 || H != 4) return;                  // (the folded form is built for config 4's shape; cross_fold_on() says the same)
-  MLD_LAUNCH((cross_fold_kernel<512, 128>), dim3((unsigned)ntok, (unsigned)H, (unsigned)L), dim3(256), kCrossFoldLdsBytes, c.stream, kv, kv_layer_stride,
-             e->ndec[0].cin_w, e->ndec[0].cin_b, e->ndec[0].cout_w, (long long)e->ndec_layer_stride, w, u, (long long)ntok * H * D, cc, (long long)ntok * H, ntok);
-  count(c);
-  check_launch(c, "cross_fold");
+  MLD_COUNTED(c, "cross_fold", MLD_LAUNCH((cross_fold_kernel<512, 128>), dim3((unsigned)ntok, (unsigned)H, (unsigned)L), dim3(256), kCrossFoldLdsBytes, c.stream, kv, kv_layer_stride, e->ndec[0].cin_w,
+         e->ndec[0].cin_b, e->ndec[0].cout_w, (long long)e->ndec_layer_stride, w, u, (long long)ntok * H * D, cc, (long long)ntok * H, ntok));
 }
 bool cross_fold_on(const E* e) { return e->cross_fold && e->cfg.latent_dim == 512 && e->cfg.num_heads == 4 && !e->trace_on; }
 
@@ -84,10 +75,7 @@ void novae_denoiser_body(Ctx& c, int R, int T, const float* tkv, long long tkv_s
   const bool dup = cfg_dup && novae_cfg_dedup(e, R);
   const int M0 = dup ? M / 2 : M, R0 = dup ? R / 2 : R;              // rows / samples in front of layer 0's cross-attention
   gemm(c, lin_args(e->FF, KP, KP, e->WskelP, P(e, "denoiser.pose_embd.bias"), e->X0, D, M0, D));
-  MLD_LAUNCH(add_pe_mod_kernel, dim3(std::min(4096, (M0 * (D / 4) + 255) / 256)), dim3(256), 0, c.stream, e->X0,
-             P(e, "denoiser.query_pos.pe"), (long long)M0, T, D);
-  count(c);
-  check_launch(c, "add_pe_mod");
+  MLD_COUNTED(c, "add_pe_mod", MLD_LAUNCH(add_pe_mod_kernel, dim3(std::min(4096, (M0 * (D / 4) + 255) / 256)), dim3(256), 0, c.stream, e->X0, P(e, "denoiser.query_pos.pe"), (long long)M0, T, D));
   for (int l = 0; l < e->cfg.num_layers && !c.rc; ++l) {
     const DecLayerP& L = e->ndec[l];
     const bool half = dup && l == 0;
@@ -106,16 +94,11 @@ void novae_denoiser_body(Ctx& c, int R, int T, const float* tkv, long long tkv_s
       a.wx = e->XKW + (size_t)l * Bm2 * H * D; a.ux = e->XKU + (size_t)l * Bm2 * H * D; a.cx = e->XKC + (size_t)l * Bm2 * H;
       if (half) { xc = e->H1; a.src_mod = R0; }
       a.bo = L.cout_b; a.g2 = L.n2_w; a.b2 = L.n2_b; a.Y = xc; a.M = M; a.T = T;
-      MLD_LAUNCH((cross2_fold_ln_kernel<512, 128>), dim3((unsigned)(R * ((T + kC2Rows - 1) / kC2Rows))), dim3(256), kC2LdsBytes, c.stream, a);
-      count(c);
-      check_launch(c, "cross2_fold_ln");
+      MLD_COUNTED(c, "cross2_fold_ln", MLD_LAUNCH((cross2_fold_ln_kernel<512, 128>), dim3((unsigned)(R * ((T + kC2Rows - 1) / kC2Rows))), dim3(256), kC2LdsBytes, c.stream, a));
     } else {
     novae_ln(c, e->Ha, e->X0, L.n1_w, L.n1_b, e->H1, M);
     gemm(c, lin_args(e->H1, D, D, L.cin_w, L.cin_b, e->Hb, D, M, D));                    // cross-attention queries
-    MLD_LAUNCH((cross2_kernel<512, 128>), dim3((M + 3) / 4), dim3(256), 0, c.stream, (const float*)e->Hb, tkv + (size_t)l * tkv_stride,
-               (const float*)(e->XKV + (size_t)l * 2 * e->cfg.max_batch * 2 * D), e->AO, M, T);
-    count(c);
-    check_launch(c, "cross2");
+    MLD_COUNTED(c, "cross2", MLD_LAUNCH((cross2_kernel<512, 128>), dim3((M + 3) / 4), dim3(256), 0, c.stream, e->Hb, tkv + (size_t)l * tkv_stride, e->XKV + (size_t)l * 2 * e->cfg.max_batch * 2 * D, e->AO, M, T));
     gemm(c, lin_args(e->AO, D, D, L.cout_w, L.cout_b, e->Ha, D, M, D));
     novae_ln(c, e->Ha, e->H1, L.n2_w, L.n2_b, e->X0, M);
     }
@@ -134,20 +117,15 @@ void novae_denoiser_body(Ctx& c, int R, int T, const float* tkv, long long tkv_s
 void novae_pad_input(Ctx& c, const float* x, long long rows, int dup) {
   E* e = c.e;
   const int KP = novae_kp(e);
-  MLD_LAUNCH(dup_pad_rows_kernel, dim3((unsigned)std::min<long long>(8192, (rows * KP + 255) / 256)), dim3(256), 0, c.stream, x, e->FF, rows,
-             e->cfg.nfeats, KP, dup);
-  count(c);
-  check_launch(c, "dup_pad_rows");
+  MLD_COUNTED(c, "dup_pad_rows", MLD_LAUNCH(dup_pad_rows_kernel, dim3((unsigned)std::min<long long>(8192, (rows * KP + 255) / 256)), dim3(256), 0, c.stream, x, e->FF, rows, e->cfg.nfeats, KP, dup));
 }
 
 void novae_fold_text(Ctx& c, int rows) {
   E* e = c.e;
   const int D = e->cfg.latent_dim, H = e->cfg.num_heads, L = e->cfg.num_layers;
   const long long tok = (long long)2 * e->cfg.max_batch;
-  MLD_LAUNCH((cross_fold_kernel<512, 128>), dim3((unsigned)rows, (unsigned)H, (unsigned)L), dim3(256), kCrossFoldLdsBytes, c.stream, (const float*)e->XKV, tok * 2 * D,
-             e->ndec[0].cin_w, e->ndec[0].cin_b, e->ndec[0].cout_w, (long long)e->ndec_layer_stride, e->XKW, e->XKU, tok * H * D, e->XKC, tok * H, rows);
-  count(c);
-  check_launch(c, "cross_fold_text");
+  MLD_COUNTED(c, "cross_fold_text", MLD_LAUNCH((cross_fold_kernel<512, 128>), dim3((unsigned)rows, (unsigned)H, (unsigned)L), dim3(256), kCrossFoldLdsBytes, c.stream, e->XKV, tok * 2 * D,
+         e->ndec[0].cin_w, e->ndec[0].cin_b, e->ndec[0].cout_w, (long long)e->ndec_layer_stride, e->XKW, e->XKU, tok * H * D, e->XKC, tok * H, rows));
 }
 
 // text token of the memory: emb_proj(text) + mem_pos.pe[1] -> TP [rows][D], then its K|V for every layer -> XKV
@@ -185,12 +163,8 @@ int novae_steps(E* e, hipStream_t stream, int B, int T, int s0, int s1, const fl
     novae_pad_input(c, e->lat, (long long)B * T, dedup ? 1 : 2);                          // torch.cat([latents] * 2) (one copy when the halves are de-duplicated)
     const size_t Hn = (size_t)e->cfg.num_heads;
     novae_denoiser_body(c, 2 * B, T, e->TKV + (size_t)s * 2 * D, (long long)n * 2 * D, NovaeFold{e->TKW + (size_t)s * Hn * D, e->TKU + (size_t)s * Hn * D, e->TKC + (size_t)s * Hn, n}, e->feats_int, dedup);
-    MLD_LAUNCH(cfg_ddpm_step_kernel, dim3((unsigned)std::min<long long>(4096, (nel / 4 + 255) / 256)), dim3(256), 0, stream,
-               (const float*)e->feats_int, (const float*)(e->feats_int + nel), (const float*)e->lat,
-               step_noise ? step_noise + (size_t)s * nel : (const float*)nullptr, e->lat, nel, guidance,
-               ddpm_coef(e, e->timesteps[s]), seed, (unsigned)s, seed_dev);
-    count(c);
-    check_launch(c, "cfg_ddpm_step");
+    MLD_COUNTED(c, "cfg_ddpm_step", MLD_LAUNCH(cfg_ddpm_step_kernel, dim3((unsigned)std::min<long long>(4096, (nel / 4 + 255) / 256)), dim3(256), 0, c.stream, e->feats_int, e->feats_int + nel, e->lat,
+           step_noise ? step_noise + (size_t)s * nel : (const float*)nullptr, e->lat, nel, guidance, ddpm_coef(e, e->timesteps[s]), seed, (unsigned)s, seed_dev));
   }
   return c.rc;
 }

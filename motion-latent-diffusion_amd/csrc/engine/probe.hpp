@@ -2,7 +2,7 @@
 // handle on one seeded probe batch; a stage that disagrees (or is not finite) is switched to the fp32 kernels.  Four stages -- the reverse
 // loop, the decoder, the diffusion-only denoiser, the CLIP text tower -- over one seeded generator and the helpers at the top.
 // Part of libmldhip's single translation unit (included by ../mldhip.hip, in this order: state, params, dispatch,
-// path_latent, path_novae, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace).
+// path_loop, streams, path_vae, path_latent, path_novae, path_clip, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace).
 #pragma once
 
 namespace {

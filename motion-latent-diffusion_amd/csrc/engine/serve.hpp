@@ -1,7 +1,7 @@
 // The sampling drivers behind the C ABI: the single call (sample_impl), the coalesced and the pipelined form of mldhip_sample_many, the one-step
 // denoiser calls, the diffusion-only call, and the cluster loop's self-healing; the short host sequences they share are the helpers at the top.
 // Part of libmldhip's single translation unit (included by ../mldhip.hip, in this order: state, params, dispatch,
-// path_latent, path_novae, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace).
+// path_loop, streams, path_vae, path_latent, path_novae, path_clip, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace).
 #pragma once
 
 namespace {

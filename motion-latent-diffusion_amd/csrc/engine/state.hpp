@@ -1,6 +1,6 @@
 // Engine state: parameter table entries, per-layer weight views, workspace contexts, the handle struct.
 // Part of libmldhip's single translation unit (included by ../mldhip.hip, in this order: state, params, dispatch,
-// path_latent, path_novae, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace) except the handle type itself.
+// path_loop, streams, path_vae, path_latent, path_novae, path_clip, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace) except the handle type itself.
 #pragma once
 
 namespace {
@@ -98,7 +98,7 @@ struct mldhip_engine {
   unsigned* cl_host_status = nullptr;   // pinned host word the cluster kernel sets next to its sticky status word: read at the start of every sample call (no device synchronisation) -- a timed-out handle leaves the cluster loop by itself
   bool cluster_foreign = false;   // another PROCESS holds the cluster lane of this device (lock file taken at mldhip_create): this handle never launches the cluster loop
   int cluster_failed = 0;         // a cluster launch reported a timeout / a placement it cannot use: the handle stays on the other loop families
-  float* arena_x3 = nullptr;  // split-bf16 image of the arena (precision modes with split-bf16 staged GEMMs; built by finalize)
+  float* arena_x3 = nullptr;  // split-f16 (hi | lo half) image of the arena (precision modes with split-f16 staged GEMMs; built by finalize)
   size_t arena_floats = 0;
   std::vector<EncLayerP> den;      // execution order
   std::vector<DecLayerP> dec;
@@ -157,7 +157,7 @@ struct mldhip_engine {
   int fused_dbg = 0;         // "fused_dbg": 5 = the split-mode loop with its phase counters (same arithmetic, mldhip_profile_trace "den_loop_phases"); 0 = off
   int fused_min_batch = 0;   // "fused_min_batch": auto picks the sample-major loop from this many motions per call up; 0 = by operand format (320 split-f16, 1 280 fp32)
   int strip_min_rows = 768;  // "strip_min_rows": auto switches to the throughput kernels at 6B >= this many token rows
-  int flash_attn = 1;        // "flash_attn": split-bf16 frame-level self-attention key-blocked (attention.hpp attn_flash_x3_kernel): 0 never, 1 auto (>= 512 (sample, head) pairs), 2 always
+  int flash_attn = 1;        // "flash_attn": split-f16 frame-level self-attention key-blocked (attention.hpp attn_flash_x3_kernel): 0 never, 1 auto (>= 512 (sample, head) pairs), 2 always
   int ffn_strip = 1;         // "ffn_strip": register-direct decoder kernels (ffn_strip.hpp, gemm_strip_x3.hpp): 0 off, 1 auto strip height, 4 / 6 = 64 / 96 rows always
   int dec_tail = 1;          // "dec_tail": out-projection + norms + feed-forward block of a decoder layer as one launch (chip-filling launches, split modes)
   int dec_l0_once = 1;       // "dec_l0_once": decoder layer 0 projects its input -- the positional rows, the same for every sample -- once per call ([T] rows instead of [B T])

@@ -154,12 +154,12 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const float* __res
 
 
 // ----------------------------------------------------------------------------------------------
-// Split-bf16 form of attn_decode_kernel (MLDHIP_PREC_BF16X3_DECODE and the other modes that run the decoder GEMMs on
-// bf16 MFMAs): same one-workgroup-per-(sample, head) structure, same swapped QK^T / P-as-A-operand mapping, but every
-// product runs as x = hi + lo in bf16 on v_mfma_f32_16x16x32_bf16 (3 MFMAs per 32-wide contraction chunk: lo*hi, hi*lo,
+// Split-f16 form of attn_decode_kernel (MLDHIP_PREC_F16X3 and the other modes that run the decoder GEMMs on
+// 16-bit MFMAs): same one-workgroup-per-(sample, head) structure, same swapped QK^T / P-as-A-operand mapping, but every
+// product runs as x = hi + lo in IEEE half on v_mfma_f32_16x16x32_f16 (3 MFMAs per 32-wide contraction chunk: lo*hi, hi*lo,
 // hi*hi; fp32 accumulate) -- 6 + 6.5 MFMAs of 16 cycles per 16 x 16 score / 16 x 64 output tile pair instead of 16 + 16 fp32
 // ones of 32 cycles.  Softmax, the 1/sqrt(d) scaling and the normalisation stay fp32.
-//   K   in LDS as two bf16 planes [key][64 dims] (row stride 40 words): lane (r, g) reads dims 32c + 8g .. + 7 of key r.
+//   K   in LDS as two half planes [key][64 dims] (row stride 40 words): lane (r, g) reads dims 32c + 8g .. + 7 of key r.
 //   V^T in LDS as two bf16 planes [dim][keys]: the P.V contraction runs over 32 KEYS per MFMA; a lane's 8 k-slots are the
 //        keys it already holds scores for -- 16kt + 4g + {0..3} of the two key tiles (2kb, 2kb + 1) -- so P needs no shuffle,
 //        and the matching V operand is two 8-byte reads of 4 consecutive keys each from the transposed planes.

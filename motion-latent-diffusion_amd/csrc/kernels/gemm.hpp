@@ -41,7 +41,7 @@ struct GemmArgs {
   const float* cvec = nullptr; int ldcvec = 0;           // + cvec[row / rows_per_group] then LN(g2,b2)
   const float* g2 = nullptr; const float* b2 = nullptr;
   unsigned long long* trace = nullptr;   // measurement only (staged kernels): 8 timestamps per wave
-  int w_split = 0;                       // PREC_BF16X3: W points into the pre-split copy of the weight arena (elementwise.hpp split_bf16_weights_kernel)
+  int w_split = 0;                       // PREC_F16X3: W points into the pre-split copy of the weight arena (elementwise.hpp split_bf16_weights_kernel)
 };
 
 struct Frag { float v[8]; };
@@ -121,8 +121,8 @@ constexpr int gemm_lds_bytes() {    // the chunk double buffer, or the output ti
 //                 flight while chunk k's MFMAs run; one barrier per chunk.  (The register-direct form
 //                 reached only ~50 of 157 TF on the decoder: fragment-shaped loads saturate the TA path,
 //                 cdna_hip_programming.md "x through LDS in full lines".)
-// PREC (staged path only): PREC_F32 = exact fp32 MFMA; PREC_BF16X3 = split-bf16 (rt.hpp): operands are split into
-//                 bf16 hi/lo planes while they are written to LDS (same LDS footprint as fp32), 3 bf16 MFMAs
+// PREC (staged path only): PREC_F32 = exact fp32 MFMA; PREC_F16X3 = split-f16 (rt.hpp): operands are split into
+//                 half hi/lo planes while they are written to LDS (same LDS footprint as fp32), 3 f16 MFMAs
 //                 per tile per K chunk; PREC_BF16 = operands rounded to bf16 (RNE) at the LDS store, one
 //                 v_mfma_f32_16x16x32_bf16 per tile and chunk.  Accumulation, bias,
 //                 residual, LayerNorm and the stored result are fp32 in every mode.
@@ -332,7 +332,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs p) {
       if constexpr (PREC == PREC_F32) {
         lfrags(buf);
         compute(fa0, fb0);
-      } else if constexpr (PREC == PREC_BF16X3) {
+      } else if constexpr (PREC == PREC_F16X3) {
         lfrags_bf16(buf);
         compute_bf16();
       } else {

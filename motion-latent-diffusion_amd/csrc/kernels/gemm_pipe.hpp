@@ -15,7 +15,7 @@
 // fragment set (the reload reuses the registers), RD chunks of global loads in flight across barriers (workgroup-scope fences do not
 // drain vmcnt outside tgsplit mode).
 //
-// Operands: X fp32 [M][K] (split into half planes while it is written to LDS, like gemm_kernel's PREC_BF16X3 path); W the pre-split
+// Operands: X fp32 [M][K] (split into half planes while it is written to LDS, like gemm_kernel's PREC_F16X3 path); W the pre-split
 // image of the weight arena (elementwise.hpp split_bf16_weights_kernel; GemmArgs::w_split must be set).  Output through an LDS tile
 // with 16-byte stores (gemm.hpp store_tile_from_lds).
 //

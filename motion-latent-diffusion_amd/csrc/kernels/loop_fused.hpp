@@ -18,7 +18,7 @@
 //   instructions, at 56 %; attention scores + softmax, the two LayerNorm phases and the skip handling -- no matrix work at all -- take
 //   a quarter of the time.  The epilogues of a phase cannot overlap the next phase's products, which depend on them.
 // It wins once a call carries enough motions to give most CUs a workgroup (2 048 motions = 256 workgroups = one per CU); below
-// a few hundred motions the column-split families finish sooner (path_latent.hpp use_fused).
+// a few hundred motions the column-split families finish sooner (path_loop.hpp use_fused).
 //
 // Row order inside the workgroup: row = 16 t + c, t = token, c = row of the CFG batch (c < 8: unconditional half of the 8
 // motions, c >= 8: conditional half).  A 16-row MFMA tile is then ONE token of all 16 CFG rows.  Every product is taken TRANSPOSED

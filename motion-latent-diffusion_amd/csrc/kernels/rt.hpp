@@ -372,7 +372,7 @@ __device__ __forceinline__ f32x4 mfma_x3_16x16x32(U4 a, U4 b, f32x4 c) {
 
 // ---- reduced-precision operand formats of the GEMM kernels (operands only: accumulation, bias, residual, LayerNorm,
 // softmax and every stored activation stay fp32).  PREC codes shared by gemm.hpp / tile32.hpp / strip.hpp:
-enum : int { PREC_F32 = 0, PREC_BF16X3 = 1, PREC_BF16 = 2 };      // (3 was PREC_FP8: retired in round 6 with the mode, include/mldhip.h)
+enum : int { PREC_F32 = 0, PREC_F16X3 = 1, PREC_BF16 = 2 };      // (3 was PREC_FP8: retired in round 6 with the mode, include/mldhip.h)
 
 // two floats -> packed bf16 pair, round-to-nearest-even (v_cvt_pk_bf16_f32 on gfx950), element 0 in the low half
 __device__ __forceinline__ unsigned pack_bf16x2(float a, float b) {

@@ -46,7 +46,7 @@ struct Tile32Args {
   float* P = nullptr;            // partial epilogue when non-null: P[z][M][N] = acc (raw)
   long long pstride = 0;
   int M = 0, N = 0;
-  int w_split = 0;               // PREC_BF16X3: W points into the pre-split (hi | lo half) image of the weight arena (elementwise.hpp)
+  int w_split = 0;               // PREC_F16X3: W points into the pre-split (hi | lo half) image of the weight arena (elementwise.hpp)
   unsigned long long* trace = nullptr;   // measurement only: 8 timestamps per wave (see mldhip_profile_trace)
 };
 
@@ -65,7 +65,7 @@ __device__ __forceinline__ void st_operand(float* row, int lane, F4 v) {
   } else if constexpr (PREC == PREC_BF16) {
     *reinterpret_cast<U2*>(reinterpret_cast<unsigned*>(row) + lane * 2) = U2{pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w)};
   } else {
-    static_assert(PREC == PREC_BF16X3, "operand format");
+    static_assert(PREC == PREC_F16X3, "operand format");
     // split-f16 image, the one split_bf16_weights_kernel writes: per 32-wide K chunk 16 words of high halves, then 16 of low halves
     unsigned h0, l0, h1, l1;
     split16_pair(v.x, v.y, h0, l0);
@@ -80,7 +80,7 @@ __device__ __forceinline__ void st_operand(float* row, int lane, F4 v) {
 // cross terms in acc0 and the hi x hi term in acc1)
 template <int PREC>
 __device__ __forceinline__ void mma_chunk(const float* arow, const float* wrow, int kc, int g, f32x4& acc0, f32x4& acc1) {
-  if constexpr (PREC == PREC_BF16X3) {
+  if constexpr (PREC == PREC_F16X3) {
     const U4* ar = reinterpret_cast<const U4*>(arow) + kc * 8 + g;
     const U4* wr = reinterpret_cast<const U4*>(wrow) + kc * 8 + g;
     const U4 ah = ar[0], al = ar[4], wh = wr[0], wl = wr[4];
@@ -131,7 +131,7 @@ __device__ __forceinline__ F4 f4add(F4 a, F4 b) { return F4{a.x + b.x, a.y + b.y
 // wait per element -- cdna_hip_programming.md, "three .s-level traps" (c)).
 // (Passing K through LDS in two 128-wide pieces so that two workgroups fit a CU was measured: +2.9 % with four batches in
 // flight, -10 % for one batch; removed -- kernels/strip.hpp is the throughput form.  profiles/r01_v17_xcd_kh_ab.txt.)
-// PREC: operand format of the MFMAs (rt.hpp PREC_F32 / PREC_BF16 / PREC_BF16X3 = split-f16, 3 MFMAs of 16 cycles per 32-wide
+// PREC: operand format of the MFMAs (rt.hpp PREC_F32 / PREC_BF16 / PREC_F16X3 = split-f16, 3 MFMAs of 16 cycles per 32-wide
 // K chunk instead of 8 of 32; the A prologue and the epilogue stay fp32).
 // MODE: how the A rows are obtained is a COMPILE-TIME property of the launch.  NS0 = 0: MODE 0 = plain rows (src[0] / src[1] by K slice),
 // MODE 1 = 3-token attention outputs; NS0 > 0: MODE 0 = every K slice combines src[0]'s slabs, MODE 1 = slices >= nz0 read src[1] as
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tile32_kernel(Tile32Args p) {
   static_assert(MODE == 0 || MODE == 1, "source mode");
   constexpr bool kAttn = NS0 == 0 && MODE == 1;       // A rows = attention outputs
   constexpr bool kTwo = NS0 > 0 && MODE == 1;         // combine source + a plain second source
-  static_assert(PREC == PREC_F32 || PREC == PREC_BF16 || PREC == PREC_BF16X3, "operand format");
+  static_assert(PREC == PREC_F32 || PREC == PREC_BF16 || PREC == PREC_F16X3, "operand format");
   constexpr int RPW = MT / 8;                 // A rows assembled per wave
   constexpr int KW = 256, ST = kT32Stride;    // K columns resident in LDS, LDS row stride (floats)
 #if defined(MLDHIP_SIM)
@@ -297,10 +297,10 @@ __global__ __launch_bounds__(512, 2) void gemm_tile32_kernel(Tile32Args p) {
   {
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-      if constexpr (PREC == PREC_BF16X3) break;
+      if constexpr (PREC == PREC_F16X3) break;
       st_operand<PREC>(Ws + (wave + i * 8) * ST, lane, wreg[i]);
     }
-    if constexpr (PREC == PREC_BF16X3) {
+    if constexpr (PREC == PREC_F16X3) {
       if (p.w_split) {                          // W came from the pre-split image: the loaded words ARE the row image
 #pragma unroll
         for (int i = 0; i < 8; ++i) st4(Ws + (wave + i * 8) * ST + lane * 4, wreg[i]);

@@ -11,7 +11,8 @@
 //                hipGraph and replayed: the 50-step loop has no host work and no host<->device sync.
 //
 // Source layout: engine/state.hpp (handle, contexts) -> engine/params.hpp (weight contract, schedules) ->
-// engine/dispatch.hpp (kernel selection) -> engine/path_latent.hpp / engine/path_novae.hpp / engine/path_clip.hpp (the model paths, the text tower) ->
+// engine/dispatch.hpp (kernel selection, the counted launch) -> engine/path_loop.hpp (the latent models' reverse loop) -> engine/streams.hpp (finalize-time weight
+// images) -> engine/path_vae.hpp (VAE decode / encode, feats2joints) -> engine/path_latent.hpp / engine/path_novae.hpp / engine/path_clip.hpp (the sample calls, the text tower) ->
 // engine/graphs.hpp (graph capture and caches) -> engine/create.hpp (validation, workspace carve, LDS registration, teardown) ->
 // engine/serve.hpp (the sampling drivers and their shared host sequences) -> engine/probe.hpp (range probe) -> the C ABI below: each
 // entry point is its argument checks and a call into the engine.  kernels/*.hpp hold the device code (no __global__ in this file).
@@ -56,6 +57,9 @@ using namespace mld;
 #include "engine/state.hpp"
 #include "engine/params.hpp"
 #include "engine/dispatch.hpp"
+#include "engine/path_loop.hpp"
+#include "engine/streams.hpp"
+#include "engine/path_vae.hpp"
 #include "engine/path_latent.hpp"
 #include "engine/path_novae.hpp"
 #include "engine/path_clip.hpp"
@@ -215,7 +219,7 @@ int mldhip_set_option(mldhip_handle* e, const char* name, int64_t value) {
   } else if (n == "dec_half") {
     if (value < 0 || value > 6 || value == 3 || value == 5) return e->fail(MLDHIP_EINVAL, "dec_half must be 0 (fp32 Q|K|V, split x3 products), 1 (half Q|K|V; strip height by launch size), 4 or 6 (1 with 64- / 96-row in-projection strips always) or 2 (1, but never overruled by finalize's probe)");
     // the probe's reading of the form is part of finalize: switching it on (with the veto in force) on a probed handle that has not read it asks for finalize again
-    if (value != 0 && value != 2 && e->finalized && e->range_probe && e->cfg.precision == MLDHIP_PREC_BF16X3_DECODE && e->probe_err_decode >= 0.f && e->probe_err_decode_half < 0.f) e->finalized = false;
+    if (value != 0 && value != 2 && e->finalized && e->range_probe && e->cfg.precision == MLDHIP_PREC_F16X3 && e->probe_err_decode >= 0.f && e->probe_err_decode_half < 0.f) e->finalized = false;
     e->dec_half = (int)value;
   } else if (n == "tile_x3") {
     if (value != 0 && value != 1) return e->fail(MLDHIP_EINVAL, "tile_x3 must be 0 or 1");
@@ -276,8 +280,8 @@ int mldhip_finalize_weights(mldhip_handle* e, void* stream_) {
   Ctx c{e, stream};
   const int D = e->cfg.latent_dim, TD = time_width(e), n = e->cfg.num_inference_steps;
   HIP_TRY(e, hipDeviceSynchronize());                   // no call may be in flight on any context while tables are rebuilt
-  if (e->cfg.precision == MLDHIP_PREC_BF16X3_DECODE) {
-    // the staged GEMMs of these modes run on split-bf16 MFMAs: split the weights once, here, not in every workgroup
+  if (e->cfg.precision == MLDHIP_PREC_F16X3) {
+    // the staged GEMMs of these modes run on split-f16 MFMAs: split the weights once, here, not in every workgroup
     if (!e->arena_x3 && hipMalloc((void**)&e->arena_x3, e->arena_floats * sizeof(float)) != hipSuccess) return e->fail(MLDHIP_EHIP, "hipMalloc(split weights)");
     const long long groups = (long long)((e->arena_floats + 31) / 32);   // arena_floats is a multiple of kAlign = 64
     MLD_LAUNCH(split_bf16_weights_kernel, dim3((unsigned)((groups + 15) / 16)), dim3(256), 0, stream, e->arena, e->arena_x3, groups);
@@ -330,7 +334,7 @@ int mldhip_finalize_weights(mldhip_handle* e, void* stream_) {
   e->finalized = true;
   e->split_loop_ok = e->split_decode_ok = e->dec_half_ok = e->text_split_ok = true;
   e->probe_err_loop = e->probe_err_decode = e->probe_err_decode_half = e->probe_err_text = -1.f;
-  if (e->cfg.precision == MLDHIP_PREC_BF16X3_DECODE && e->range_probe) {
+  if (e->cfg.precision == MLDHIP_PREC_F16X3 && e->range_probe) {
     if (int rc = range_probe(e, stream)) { e->finalized = false; return rc; }
     e->probe_first_call = e->range_probe == 2;
   }
@@ -351,14 +355,14 @@ int mldhip_numeric_status(mldhip_handle* e, mldhip_numeric_info* out) {
   // (the captured graphs that hold it are dropped); mldhip_set_option("loop_kernel", 4) re-arms it
   if (!e->cluster_failed && cluster_timed_out(e)) leave_cluster_loop(e);
   out->probed = e->probe_err_loop >= 0.f || e->probe_err_decode >= 0.f || e->probe_err_text >= 0.f;
-  out->loop_split_ok = e->cfg.precision == MLDHIP_PREC_BF16X3_DECODE && e->split_loop_ok;
-  out->decode_split_ok = e->cfg.precision == MLDHIP_PREC_BF16X3_DECODE && e->split_decode_ok;
+  out->loop_split_ok = e->cfg.precision == MLDHIP_PREC_F16X3 && e->split_loop_ok;
+  out->decode_split_ok = e->cfg.precision == MLDHIP_PREC_F16X3 && e->split_decode_ok;
   out->probe_err_loop = e->probe_err_loop;
   out->probe_err_decode = e->probe_err_decode;
   out->nonfinite_values = (int64_t)n;
   out->cluster_loop = !e->cl_stream ? 0 : e->cluster_foreign ? 3 : e->cluster_failed ? 2 : 1;
   out->reserved = 0;
-  out->decode_half_ok = e->cfg.precision == MLDHIP_PREC_BF16X3_DECODE && e->split_decode_ok && e->dec_half && (e->dec_half_ok || e->dec_half == 2);
+  out->decode_half_ok = e->cfg.precision == MLDHIP_PREC_F16X3 && e->split_decode_ok && e->dec_half && (e->dec_half_ok || e->dec_half == 2);
   out->probe_err_decode_half = e->probe_err_decode_half;
   if (out->struct_size > kInfoAbi7) {
     out->text_split_ok = e->cfg.clip_layers > 0 && e->cfg.precision == MLDHIP_PREC_F16X3 && e->arena_x3 && e->text_split_ok;
@@ -610,7 +614,7 @@ int mldhip_profile_kernel(mldhip_handle* e, const char* name, int32_t B, int32_t
       f1.act = ACT_GELU;
       gemm(c, f1);
       *flops_per_launch = 2.0 * M * D * F;
-    } else if (n == "dec_ffn") {      // the whole feed-forward block as the layer runs it (one fused launch in the split-bf16 modes)
+    } else if (n == "dec_ffn") {      // the whole feed-forward block as the layer runs it (one fused launch in the split-f16 mode)
       ffn_block(c, e->H1, e->Hb, (int)M, e->dec[mid].l1_w, e->dec[mid].l1_b, e->dec[mid].l2_w, e->dec[mid].l2_b, e->dec[mid].n3_w, e->dec[mid].n3_b, 0);
       *flops_per_launch = 4.0 * M * D * F;
     } else if (n == "dec_ffn2_ln") {

@@ -30,7 +30,7 @@ using namespace mld;
 #ifdef GB_PIPE      // the software-pipelined big-tile kernel (kernels/gemm_pipe.hpp), 1-D XCD-aware grid
 #define GB_KERNEL gemm_pipe_x3_kernel<GB_TILE, GB_K / 32, GB_RD>
 #else
-#define GB_KERNEL gemm_kernel<GB_TILE, false, true, PREC_BF16X3, GB_K / 32>
+#define GB_KERNEL gemm_kernel<GB_TILE, false, true, PREC_F16X3, GB_K / 32>
 #endif
 constexpr int kTile[4] = {GB_TILE};
 constexpr int kBM = kTile[0] * kTile[2] * 16, kBN = kTile[1] * kTile[3] * 16, kNT = kTile[0] * kTile[1] * 64;
