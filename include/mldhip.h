@@ -401,6 +401,27 @@ typedef struct mldhip_noise_key {
 int mldhip_sample_many_seeded(mldhip_handle* h, const mldhip_request* reqs, const mldhip_noise_key* keys, int32_t nreq,
                               void* stream);
 
+/* Per-step latent trajectories (added at ABI 8 WITHOUT a version bump: one more symbol, no struct changed -- callers detect it by
+ * its presence, dlsym / hasattr).  Replaces: MLD._diffusion_reverse_tsne (mld/models/modeltype/mld.py:362-424), the reverse loop that
+ * returns the latents after every scheduler step -- here read out of the loop that serves the call, whichever family that is (one
+ * 1 KB row store per motion and step from the registers that hold the step's result; no extra launch).
+ *   traj_out_dev      [nreq] device pointers; entry i: [num_inference_steps][B_i][latent_size * latent_dim] floats, or NULL (no trajectory
+ *                     for request i).  Row s holds the latents of request i's motions after scheduler step s (0-based, loop order), i.e.
+ *                     prev_sample of step s: row num_inference_steps - 1 equals latents_out to the bit (also behind a cluster launch that ran
+ *                     into its wait bound: NaN in both).  Every non-NULL entry must be 16-byte aligned (the kernels store a row four floats at
+ *                     a time, straight into the caller's buffer; any hipMalloc / torch allocation is): MLDHIP_EINVAL otherwise.
+ *   keys              one mldhip_noise_key per request, as for mldhip_sample_many_seeded; may be NULL on an eta = 0 handle (nothing is drawn),
+ *                     MLDHIP_EINVAL on an eta > 0 one.
+ * traj_out_dev NULL, or every entry NULL: the call IS mldhip_sample_many_seeded -- same path, same captured graphs, same bits.  Otherwise the
+ * path rules of mldhip_sample_many apply (text and action engines, eta = 0 and eta > 0, every loop family) with one exception: a call that
+ * asks for any trajectory runs as ONE chain over all its motions even under "many_pipeline" 1 (sum of B <= max_batch).  Latents, features and
+ * joints of such a call are bit-identical to the same call without trajectories on that path.  The buffers are reached through an engine-owned
+ * table uploaded with every call, so the captured graph of the shape is replayed whatever buffers the caller passes.
+ * The diffusion-only variant (MLDHIP_VAE_NONE) refuses a non-NULL trajectory with MLDHIP_EINVAL. */
+int mldhip_sample_many_traj(mldhip_handle* h, const mldhip_request* reqs, const mldhip_noise_key* keys /* NULL on an eta = 0 handle */,
+                            float* const* traj_out_dev /* [nreq]; entry i: [num_inference_steps][B_i][latent_size * latent_dim] or NULL */,
+                            int32_t nreq, void* stream);
+
 /* Replaces: MldDenoiser.forward(sample, timestep, encoder_hidden_states)[0]
  * (mld/models/architectures/mld_denoiser.py:135-228).  sample [R,1,D], text [R,1,text_dim],
  * out [R,1,D]; any integer timestep in [0, num_train_timesteps). */

@@ -363,8 +363,10 @@ int create_engine(const mldhip_config& cfg, int device, int num_cus, mldhip_hand
     if (hipMemset(x.ws, 0, want.off * sizeof(float)) != hipSuccess) return fail_create("hipMemset(workspace) failed");
     if (hipMalloc((void**)&x.lens, 2 * Bm * sizeof(int32_t)) != hipSuccess || hipMalloc((void**)&x.lens2, Bm * sizeof(int32_t)) != hipSuccess ||
         hipMalloc((void**)&x.labels, 2 * Bm * sizeof(int32_t)) != hipSuccess || hipMalloc((void**)&x.keys, Bm * sizeof(NoiseKey)) != hipSuccess ||
-        hipMemset(x.keys, 0, Bm * sizeof(NoiseKey)) != hipSuccess) return fail_create("hipMalloc(lens) failed");
+        hipMemset(x.keys, 0, Bm * sizeof(NoiseKey)) != hipSuccess || hipMalloc((void**)&x.traj, Bm * sizeof(TrajRow)) != hipSuccess ||
+        hipMemset(x.traj, 0, Bm * sizeof(TrajRow)) != hipSuccess) return fail_create("hipMalloc(lens) failed");
     x.keys_host.assign(Bm, NoiseKey{0ull, 0ll});
+    x.traj_host.assign(Bm, TrajRow{nullptr, 0ll});
 #if !defined(MLDHIP_SIM)
     for (hipEvent_t* ev : x.events())
       if (hipEventCreateWithFlags(ev, hipEventDisableTiming) != hipSuccess) return fail_create("event create failed");

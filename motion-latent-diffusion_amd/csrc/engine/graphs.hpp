@@ -74,9 +74,11 @@ int graph_for(E* e, const GraphKey& key, bool text_condition, hipGraphExec_t* ou
         return cd.rc;
       }
       e->sample_part = key.part;
+      e->traj_on = key.traj;
       const int r = enqueue_sample(e, e->cap_stream, text_condition ? e->text_in : nullptr, e->lat_in, key.B, key.T, nullptr,
                                    key.feats ? e->feats_int : nullptr, key.joints ? e->joints_int : nullptr);
       e->sample_part = 0;
+      e->traj_on = false;
       return r;
     });
     if (rc) return rc;

@@ -18,7 +18,7 @@ using E = mldhip_engine;
 void bind_context(E* e, int k) {
   WsContext& x = e->ctxs[k];
   for (auto& cv : e->carve) *cv.first = x.ws + cv.second;
-  e->lens_dev = x.lens; e->lens2_dev = x.lens2; e->labels_dev = x.labels; e->keys_dev = x.keys;
+  e->lens_dev = x.lens; e->lens2_dev = x.lens2; e->labels_dev = x.labels; e->keys_dev = x.keys; e->traj_dev = x.traj;
   e->cur_ctx = k;
 }
 
@@ -115,6 +115,7 @@ bool is_novae(const E* e) { return e->cfg.vae_arch == MLDHIP_VAE_NONE; }
 bool is_ddpm(const E* e) { return e->cfg.scheduler_type == MLDHIP_SCHED_DDPM; }
 bool eta_on(const E* e) { return e->cfg.eta > 0.0f; }                       // stochastic DDIM handle (sampling needs noise keys)
 bool eta_live(const E* e) { return eta_on(e) && !e->noise_off; }            // ... and the reverse loop being issued draws noise
+const TrajRow* traj_table(const E* e) { return e->traj_on ? e->traj_dev : nullptr; }   // what the reverse loop being issued gets as its trajectory table
 int novae_kp(const E* e) { return (e->cfg.nfeats + 127) / 128 * 128; }   // feature width padded to 4 K chunks (263 -> 384)
 int vae_layers(const E* e) { return is_actor(e) ? (e->cfg.vae_num_layers > 0 ? e->cfg.vae_num_layers : e->cfg.num_layers) : e->cfg.num_layers; }
 std::string actor_layer(int i) { return "vae.decoder.seqTransDecoder.layers." + std::to_string(i); }

@@ -92,10 +92,10 @@ int enqueue_sample(E* e, hipStream_t stream, const float* text, const float* ini
       const float* t1n = (s + 1 < n) ? e->T1 + (size_t)(s + 1) * D : nullptr;
       if (eta_live(e))
         MLD_COUNTED(c, "den_final_step", MLD_LAUNCH(den_final_step_eta_kernel, dim3(B), dim3(256), 0, c.stream, den_final_args(e, v), v.lat, v.X0, P(e, "denoiser.query_pos.pe"), t1n, B,
-               guidance, ddim_coef(e, e->timesteps[s]), e->keys_dev, s, ddim_eta(e, e->timesteps[s])));
+               guidance, ddim_coef(e, e->timesteps[s]), e->keys_dev, s, ddim_eta(e, e->timesteps[s]), traj_table(e)));
       else
         MLD_COUNTED(c, "den_final_step", MLD_LAUNCH(den_final_step_kernel, dim3(B), dim3(256), 0, c.stream, den_final_args(e, v), v.lat, v.X0, P(e, "denoiser.query_pos.pe"), t1n, B,
-               guidance, ddim_coef(e, e->timesteps[s])));
+               guidance, ddim_coef(e, e->timesteps[s]), traj_table(e), s));
     }
   }
   if (c.rc || e->sample_part == 2) return c.rc;    // (part 2: the launch alone; the pipelined form counts non-finite latents on its side stream, in front of the decode)

@@ -299,6 +299,7 @@ void launch_fused_loop(Ctx& c, const float* init_lat, int B, int n, float guidan
   a.stream = x3 ? e->loop_stream_x3 : e->loop_stream; a.ips = e->loop_ips; a.small = e->loop_small; a.T1 = e->T1; a.TP = e->TP; a.init_lat = init_lat;
   a.lat = e->lat; a.skip = e->FS; a.ddim = e->loop_ddim; a.B = B; a.L = e->cfg.num_layers; a.n = n;
   a.guidance = guidance; a.init_sigma = 1.0f;
+  a.traj = traj_table(e);
   const dim3 grid((B + 7) / 8);
   if (eta_live(e)) {                    // stochastic DDIM: the step's second table row + the call's noise keys
     a.eta = e->loop_eta; a.keys = e->keys_dev;
@@ -330,6 +331,7 @@ void launch_cluster_chunk(Ctx& c, const float* init_lat, int B, int s_base, int 
   a.flags = reinterpret_cast<unsigned*>(e->cl_flags);
   a.status = a.flags + (size_t)std::min<size_t>(kClMaxClusters, (e->cfg.max_batch + 7) / 8) * kClFlagWords;
   a.B = B; a.L = e->cfg.num_layers; a.n = n; a.guidance = guidance; a.init_sigma = 1.0f;
+  a.traj = traj_table(e);
 #if defined(MLDHIP_SIM)
   a.xslots = std::min(a.ncl, 8);          // the simulator creates a fiber per work-item of every block: no idle XCD slots
 #else

@@ -135,6 +135,19 @@ int upload_keys(E* e, const mldhip_request* rq, const mldhip_noise_key* keys, in
   return MLDHIP_OK;
 }
 
+// The trajectory table of a coalesced call into the bound context's array (mldhip_sample_many_traj): motion k of request i gets {traj[i] + k * D, B_i * D} -- its row
+// in step 0 of the request's [steps][B_i][D] buffer and the pitch between steps -- or {NULL, 0} when the request asked for none.  Built on the host into the context's
+// stable copy and uploaded with every call, like the keys: the kernels never see a caller pointer as a launch argument, so a captured graph replays with fresh buffers.
+int upload_traj(E* e, const mldhip_request* rq, float* const* traj, int nreq, hipStream_t stream) {
+  WsContext& x = e->ctxs[e->cur_ctx];
+  const long long D = (long long)e->cfg.latent_size * e->cfg.latent_dim;
+  int o = 0;
+  for (int i = 0; i < nreq; ++i)
+    for (int k = 0; k < rq[i].B; ++k, ++o) x.traj_host[o] = traj[i] ? TrajRow{traj[i] + k * D, rq[i].B * D} : TrajRow{nullptr, 0ll};
+  HIP_TRY(e, hipMemcpyAsync(e->traj_dev, x.traj_host.data(), (size_t)o * sizeof(TrajRow), hipMemcpyHostToDevice, stream));
+  return MLDHIP_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- mldhip_sample_many, pipelined
 // "many_pipeline": the requests of a mldhip_sample_many call ONE AFTER THE OTHER, each on the single-request path (the reverse loop of a request is one cluster
 // launch, kernels/loop_cluster.hpp) -- the reference's own shape, batch after batch (mld.py:618-672, test.py:116-119) -- with the two halves of consecutive requests
@@ -406,7 +419,9 @@ int scatter_results(Ctx& c, const mldhip_request* rq, int nreq, const std::vecto
   return check_launch(c, "scatter_results");
 }
 
-int sample_many_impl(E* e, const mldhip_request* rq, int nreq, hipStream_t stream, const mldhip_noise_key* keys = nullptr) {
+// `traj` (or nullptr): per request, the [steps][B_i][D] buffer that receives the latents after every scheduler step (mldhip_sample_many_traj); a call that asks
+// for any runs as one chain, also under "many_pipeline" 1
+int sample_many_impl(E* e, const mldhip_request* rq, int nreq, hipStream_t stream, const mldhip_noise_key* keys = nullptr, float* const* traj = nullptr) {
   if (!e->finalized) return e->fail(MLDHIP_ESTATE, "mldhip_sample_many before mldhip_finalize_weights");
   heal_cluster(e);
   const bool action = is_action(e);
@@ -428,7 +443,9 @@ int sample_many_impl(E* e, const mldhip_request* rq, int nreq, hipStream_t strea
   }
   if (!e->group_ready[0] || !e->group_ready[1] || (want_j && !e->group_ready[2]))
     return e->fail(MLDHIP_ESTATE, "mldhip_sample_many needs denoiser.*, vae.decoder.* (and mean/std for joints) loaded");
-  if (e->many_pipeline && nreq >= 2 && e->ctxs.size() >= 2) {
+  bool want_t = false;
+  for (int i = 0; traj && i < nreq; ++i) want_t = want_t || traj[i];
+  if (e->many_pipeline && nreq >= 2 && e->ctxs.size() >= 2 && !want_t) {
     bool ok = true;
     for (int i = 0; i < nreq; ++i) ok = ok && use_cluster(e, rq[i].B) && (rq[i].feats_out_dev || rq[i].joints_out_dev);
     if (ok) return sample_many_pipelined(e, rq, nreq, tmax, stream, keys);
@@ -439,6 +456,7 @@ int sample_many_impl(E* e, const mldhip_request* rq, int nreq, hipStream_t strea
   ClusterLane lane(e, stream, e->cluster_lane && use_cluster(e, Btot));
   HIP_TRY(e, hipMemcpyAsync(e->lens_dev, lens.data(), (size_t)Btot * sizeof(int32_t), hipMemcpyHostToDevice, stream));
   if (keys) if (int rc = upload_keys(e, rq, keys, 0, nreq, stream)) return rc;
+  if (want_t) if (int rc = upload_traj(e, rq, traj, nreq, stream)) return rc;
   if (action) {
     // stage_actions' layout for the gathered batch, built on the host (the requests' labels are not contiguous): one copy
     std::vector<int32_t> lab(2 * (size_t)Btot, 0);
@@ -452,11 +470,18 @@ int sample_many_impl(E* e, const mldhip_request* rq, int nreq, hipStream_t strea
 #if !defined(MLDHIP_SIM)
   if (replays(e, Btot)) {
     hipGraphExec_t exec = nullptr;
-    if (int rc = graph_for(e, GraphKey{Btot, T, want_f, want_j}, text != nullptr, &exec)) return rc;
+    GraphKey key{Btot, T, want_f, want_j};
+    key.traj = want_t;
+    if (int rc = graph_for(e, key, text != nullptr, &exec)) return rc;
     HIP_TRY(e, hipGraphLaunch(exec, stream));
   } else
 #endif
-  if (int rc = enqueue_sample(e, stream, text, e->lat_in, Btot, T, nullptr, want_f ? e->feats_int : nullptr, want_j ? e->joints_int : nullptr)) return rc;
+  {
+    e->traj_on = want_t;
+    const int rc = enqueue_sample(e, stream, text, e->lat_in, Btot, T, nullptr, want_f ? e->feats_int : nullptr, want_j ? e->joints_int : nullptr);
+    e->traj_on = false;
+    if (rc) return rc;
+  }
   return scatter_results(cio, rq, nreq, tmax, T);
 }
 

@@ -62,6 +62,9 @@ struct DdimCoef { float sqrt_at, sqrt_1mat, sqrt_ap, sqrt_1map; };   // DDIM eta
 struct DdimEta { float c_eps, sigma; };
 // Noise key of one motion of a call (include/mldhip.h "Noise contract"): z of (step i, element e) is element index * 256 + e of Philox(seed, i)
 struct NoiseKey { unsigned long long seed; long long index; };
+// Trajectory entry of one motion of a call (mldhip_sample_many_traj): the motion's row in step 0 of its request's [steps][B_i][256] buffer (NULL: no
+// trajectory for this motion) and the floats between consecutive steps (B_i x 256).  The reverse loop stores prev_sample of step s to row0 + s * step_stride.
+struct TrajRow { float* row0; long long step_stride; };
 
 // LayerNorm over rows of width 256: one wave per row, 4 rows per workgroup.
 __global__ __launch_bounds__(256) void layernorm_rows_kernel(const float* __restrict__ X, float* __restrict__ Y,

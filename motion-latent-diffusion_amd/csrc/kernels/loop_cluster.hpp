@@ -94,6 +94,7 @@ struct ClusterArgs {
   float guidance, init_sigma;
   const float* eta = nullptr;        // den_cluster_eta_kernel: [n][2] DdimEta per step
   const NoiseKey* keys = nullptr;    // ... [B] noise key per motion of the call
+  const TrajRow* traj = nullptr;     // mldhip_sample_many_traj: [B] trajectory entry per motion of the call, or NULL; member 0 stores, as with `lat`
 };
 
 #if defined(MLDHIP_SIM)

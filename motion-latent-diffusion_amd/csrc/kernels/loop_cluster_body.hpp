@@ -128,7 +128,13 @@
     if (member == 0) {
       const int c = tid >> 6, c4 = tid & 63;
       const float qnan = __builtin_nanf("");
-      if (s0 + c < p.s_end) st4(p.lat + (long long)(s0 + c) * 256 + c4 * 4, F4{qnan, qnan, qnan, qnan});
+      if (s0 + c < p.s_end) {
+        st4(p.lat + (long long)(s0 + c) * 256 + c4 * 4, F4{qnan, qnan, qnan, qnan});
+        if (p.traj) {                  // ... and the last trajectory row of its motions: traj[n - 1] == lat also behind a failed launch
+          const TrajRow tr = p.traj[s0 + c];
+          if (tr.row0) st4_global(tr.row0 + (long long)(p.n - 1) * tr.step_stride + c4 * 4, F4{qnan, qnan, qnan, qnan});
+        }
+      }
     }
   };
 
@@ -731,6 +737,11 @@
         }
         }
         st4(lp, F4{nv[0], nv[1], nv[2], nv[3]});
+        // the step's prev_sample to the motion's trajectory row: member 0 (as with p.lat), wave w = motion s0 + w (wave-uniform test; no barrier, no LDS)
+        if (member == 0 && p.traj && s0 + wave < p.s_end) {
+          const TrajRow tr = p.traj[s0 + wave];
+          if (tr.row0) st4_global(tr.row0 + (long long)step * tr.step_stride + lane * 4, F4{nv[0], nv[1], nv[2], nv[3]});
+        }
         prm_store(pbuf ^ 1);
         if (step + 1 < p.n) assemble(step + 1);      // (reads this wave's own latent row only)
         __syncthreads();

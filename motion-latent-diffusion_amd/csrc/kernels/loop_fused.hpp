@@ -74,6 +74,7 @@ struct LoopArgs {
   unsigned long long* trace = nullptr;   // DBG 5 (measurement build): [workgroup < 64][wave][8] shader cycles per phase, summed over steps and layers
   const float* eta = nullptr;            // den_loop_kernel<X3, kLoopEta>: [n][2] DdimEta per step
   const NoiseKey* keys = nullptr;        // ... [B] noise key per motion of the call
+  const TrajRow* traj = nullptr;         // mldhip_sample_many_traj: [B] trajectory entry per motion of the call, or NULL (no trajectory: nothing is stored)
 };
 
 // den_loop_kernel<X3, kLoopEta>: the stochastic-DDIM form (eta > 0, include/mldhip.h "Noise contract") of the production loop.  It takes a value of
@@ -788,6 +789,13 @@ __global__ __launch_bounds__(512, 2) void den_loop_kernel(LoopArgs p) {
             }
             }
             st4(lp, F4{nv[0], nv[1], nv[2], nv[3]});
+            // the step's prev_sample to the motion's trajectory row (no barrier, no LDS: the values are in registers; real motions only).  p.traj is
+            // wave-uniform; the motion test is per lane here (r = lane & 15: a wave holds the 8 motions of the workgroup, unlike the cluster loop's one
+            // motion per wave), so the 16-byte table entry is a per-lane load of 8 distinct addresses, and the lanes of missing motions are masked off
+            if (p.traj && s0 + r < p.B) {
+              const TrajRow tr = p.traj[s0 + r];
+              if (tr.row0) st4_global(tr.row0 + (long long)step * tr.step_stride + (cb * 128 + cq0), F4{nv[0], nv[1], nv[2], nv[3]});
+            }
           }
         }
         __syncthreads();

@@ -260,6 +260,22 @@ __device__ __forceinline__ void st4_nt(float* p, F4 v) {
   __builtin_nontemporal_store(__builtin_bit_cast(f32x4, v), reinterpret_cast<f32x4*>(p));
 #endif
 }
+// stores through a pointer that was itself LOADED from device memory (the trajectory table's rows): the compiler cannot see its address space and would emit
+// flat stores; the pointer is a hipMalloc'd buffer, i.e. global memory -- say so (global_store; the simulator has one address space)
+__device__ __forceinline__ void st4_global(float* p, F4 v) {
+#if defined(MLDHIP_SIM)
+  st4(p, v);
+#else
+  *(__attribute__((address_space(1))) f32x4*)(p) = __builtin_bit_cast(f32x4, v);
+#endif
+}
+__device__ __forceinline__ void st1_global(float* p, float v) {
+#if defined(MLDHIP_SIM)
+  *p = v;
+#else
+  *(__attribute__((address_space(1))) float*)(p) = v;
+#endif
+}
 template <bool NT_>
 __device__ __forceinline__ F4 ld4_hint(const float* p) { if constexpr (NT_) return ld4_nt(p); else return ld4(p); }
 template <bool NT_>

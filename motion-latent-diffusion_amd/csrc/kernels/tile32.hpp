@@ -368,6 +368,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tile32_kernel(Tile32Args p) {
 // End of one reverse step.  Token-0 rows only: x = LN2(sum FFN2 slabs + b2 + h1) (last layer's norm2),
 // e = LN_final(x) (cross_attention.py:62-63, mld_denoiser.py:206), CFG (mld.py:339-342), DDIM step
 // (diffusers DDIMScheduler.step, eta 0), and the next step's token-0 / time rows.  grid = B, block = 256.
+// `traj` (or NULL): the call's trajectory table -- the step's result also goes to row `step` of the motion's trajectory buffer.
 struct FinalArgs {
   const float* P; int nsplit; long long pstride;   // last FFN2 partial slabs [nsplit][3R][256]
   const float* b2; const float* H1;                // FFN2 bias, residual rows (norm1 output)
@@ -393,7 +394,8 @@ __device__ __forceinline__ float final_row_value(const FinalArgs& f, long long r
 template <bool ETA>
 __device__ __forceinline__ void den_final_step_body(const FinalArgs& f, float* __restrict__ lat, float* __restrict__ X0,
                                                     const float* __restrict__ pe0, const float* __restrict__ t1_next,
-                                                    int B, float guidance, const DdimCoef& c, const NoiseKey* __restrict__ keys, int step, DdimEta k) {
+                                                    int B, float guidance, const DdimCoef& c, const NoiseKey* __restrict__ keys, int step, DdimEta k,
+                                                    const TrajRow* __restrict__ traj) {
   __shared__ float sh[4];
   const int b = blockIdx.x, d = threadIdx.x, R = 2 * B;
   const float eu = final_row_value(f, b, d, sh);
@@ -413,6 +415,10 @@ __device__ __forceinline__ void den_final_step_body(const FinalArgs& f, float* _
     xn = c.sqrt_ap * x0 + c.sqrt_1map * eps;
   }
   lat[(long long)b * 256 + d] = xn;
+  if (traj) {                          // mldhip_sample_many_traj: prev_sample of this step to the motion's trajectory row (block-uniform test)
+    const TrajRow tr = traj[b];
+    if (tr.row0) st1_global(tr.row0 + (long long)step * tr.step_stride + d, xn);
+  }
   const float tok = xn + pe0[d];
   X0[(long long)b * 256 + d] = tok;
   X0[(long long)(B + b) * 256 + d] = tok;
@@ -425,14 +431,15 @@ __device__ __forceinline__ void den_final_step_body(const FinalArgs& f, float* _
 
 __global__ __launch_bounds__(256) void den_final_step_kernel(FinalArgs f, float* __restrict__ lat, float* __restrict__ X0,
                                                              const float* __restrict__ pe0, const float* __restrict__ t1_next,
-                                                             int B, float guidance, DdimCoef c) {
-  den_final_step_body<false>(f, lat, X0, pe0, t1_next, B, guidance, c, nullptr, 0, DdimEta{0.f, 0.f});
+                                                             int B, float guidance, DdimCoef c, const TrajRow* __restrict__ traj, int step) {
+  den_final_step_body<false>(f, lat, X0, pe0, t1_next, B, guidance, c, nullptr, step, DdimEta{0.f, 0.f}, traj);
 }
 
 __global__ __launch_bounds__(256) void den_final_step_eta_kernel(FinalArgs f, float* __restrict__ lat, float* __restrict__ X0,
                                                                  const float* __restrict__ pe0, const float* __restrict__ t1_next,
-                                                                 int B, float guidance, DdimCoef c, const NoiseKey* __restrict__ keys, int step, DdimEta k) {
-  den_final_step_body<true>(f, lat, X0, pe0, t1_next, B, guidance, c, keys, step, k);
+                                                                 int B, float guidance, DdimCoef c, const NoiseKey* __restrict__ keys, int step, DdimEta k,
+                                                                 const TrajRow* __restrict__ traj) {
+  den_final_step_body<true>(f, lat, X0, pe0, t1_next, B, guidance, c, keys, step, k, traj);
 }
 
 // Stand-alone MldDenoiser.forward output: out[r] = LN_final(LN2(...)) for the R token-0 rows.  grid = R.

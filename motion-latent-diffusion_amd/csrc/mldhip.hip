@@ -396,6 +396,26 @@ int mldhip_sample_many_seeded(mldhip_handle* e, const mldhip_request* reqs, cons
   return sample_many_impl(e, reqs, nreq, (hipStream_t)stream_, eta_on(e) ? keys : nullptr);
 }
 
+int mldhip_sample_many_traj(mldhip_handle* e, const mldhip_request* reqs, const mldhip_noise_key* keys, float* const* traj_out_dev, int32_t nreq, void* stream_) {
+  if (!e) return MLDHIP_EINVAL;
+  DeviceGuard dg(e->device);
+  if (!reqs || nreq < 1 || nreq > 64) return e->fail(MLDHIP_EINVAL, "1..64 requests expected");
+  bool any = false;
+  for (int i = 0; traj_out_dev && i < nreq; ++i) {
+    any = any || traj_out_dev[i];
+    if (reinterpret_cast<uintptr_t>(traj_out_dev[i]) % 16) return e->fail(MLDHIP_EINVAL, "traj_out_dev[%d] is not 16-byte aligned (the rows are stored four floats at a time)", i);
+  }
+  if (is_novae(e)) {
+    if (any) return e->fail(MLDHIP_EINVAL, "mldhip_sample_many_traj: the diffusion-only variant has no latent trajectory (its loop state is the raw motion [B, T, nfeats] over 1000 steps)");
+    return e->fail(MLDHIP_ESTATE, "mldhip_sample_many_traj serves the latent models (text or action condition)");      // as mldhip_sample_many_seeded answers such a handle
+  }
+  // the keys: required where noise is drawn (as mldhip_sample_many_seeded requires them), optional and ignored on an eta = 0 handle
+  if (eta_on(e) && !keys) return e->fail(MLDHIP_EINVAL, "keys is NULL on a handle with eta > 0 (one mldhip_noise_key per request)");
+  for (int i = 0; keys && i < nreq; ++i)
+    if (keys[i].first_index < 0) return e->fail(MLDHIP_EINVAL, "keys[%d].first_index %lld is negative", i, (long long)keys[i].first_index);
+  return sample_many_impl(e, reqs, nreq, (hipStream_t)stream_, eta_on(e) ? keys : nullptr, any ? traj_out_dev : nullptr);
+}
+
 int mldhip_sample(mldhip_handle* e, const float* text_emb_dev, const float* init_latents_dev, const int32_t* lengths_host,
                   int32_t B, float* latents_out_dev, float* feats_out_dev, float* joints_out_dev, void* stream_) {
   if (!e) return MLDHIP_EINVAL;
@@ -603,7 +623,7 @@ int mldhip_profile_kernel(mldhip_handle* e, const char* name, int32_t B, int32_t
       *flops_per_launch = 2.0 * M * D * F;
     } else if (n == "den_final") {
       MLD_LAUNCH(den_final_step_kernel, dim3(B), dim3(256), 0, c.stream, den_final_args(e, v), e->zbuf, e->LNO,
-                 P(e, "denoiser.query_pos.pe"), (const float*)e->T1, B, e->cfg.guidance_scale, ddim_coef(e, e->timesteps[0]));
+                 P(e, "denoiser.query_pos.pe"), (const float*)e->T1, B, e->cfg.guidance_scale, ddim_coef(e, e->timesteps[0]), (const TrajRow*)nullptr, 0);
       check_launch(c, "den_final_step");
       *flops_per_launch = 0.0;
     } else if (n == "dec_qkv") {

@@ -83,6 +83,7 @@ _SYMBOLS = {
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "mldhip_sample_many": (C.c_int, [C.c_void_p, C.POINTER(Request), C.c_int32, C.c_void_p]),
     "mldhip_sample_many_seeded": (C.c_int, [C.c_void_p, C.POINTER(Request), C.POINTER(NoiseKey), C.c_int32, C.c_void_p]),
+    "mldhip_sample_many_traj": (C.c_int, [C.c_void_p, C.POINTER(Request), C.POINTER(NoiseKey), C.POINTER(C.c_void_p), C.c_int32, C.c_void_p]),
     "mldhip_denoiser_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "mldhip_sample_action": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
@@ -263,6 +264,17 @@ class Engine:
         arr, keep = self._requests(requests)
         ks = (NoiseKey * len(keys))(*[NoiseKey(int(s) & 0xFFFFFFFFFFFFFFFF, int(f)) for s, f in keys])
         self._check(self.lib.mldhip_sample_many_seeded(self._h, arr, ks, len(requests), stream))
+
+    def sample_many_traj(self, requests: Sequence[dict], keys: Optional[Sequence] = None, stream: int = 0):
+        """``sample_many_seeded`` that also returns the latents after every scheduler step (mldhip_sample_many_traj): a request dict may carry
+        ``traj_out``, a [num_inference_steps, B_i, latent_size * latent_dim] float32 buffer; row s = prev_sample of step s, the last row equals
+        ``latents_out`` to the bit.  ``keys`` may be None on an eta = 0 handle.  Without any ``traj_out`` the call is ``sample_many_seeded``."""
+        if keys is not None and len(keys) != len(requests):
+            raise ValueError("one (seed, first_index) key per request")
+        arr, keep = self._requests(requests)
+        ks = None if keys is None else (NoiseKey * len(keys))(*[NoiseKey(int(s) & 0xFFFFFFFFFFFFFFFF, int(f)) for s, f in keys])
+        tr = (C.c_void_p * len(requests))(*[_ptr(q.get("traj_out")) or None for q in requests])
+        self._check(self.lib.mldhip_sample_many_traj(self._h, arr, ks, tr, len(requests), stream))
 
     def _requests(self, requests: Sequence[dict]):
         arr = (Request * len(requests))()

@@ -1,6 +1,6 @@
 """``MLD`` -- the orchestrator of the sampling path with the reference's call surface
 (mld/models/modeltype/mld.py:33-143 construct, :216-265 forward, :267-275 gen_from_latent,
-:290-360 _diffusion_reverse), minus Lightning/training/metrics (out of scope).
+:290-360 _diffusion_reverse, :362-424 _diffusion_reverse_tsne), minus Lightning/training/metrics (out of scope).
 
 Two execution paths, same results:
   fused   -- every network part is a Hip* drop-in: ONE ``mldhip_sample`` call (hipGraph replay of the
@@ -132,10 +132,11 @@ class MLD(nn.Module):
     # ------------------------------------------------------------------ fused path
     @torch.no_grad()
     def sample(self, text_emb: torch.Tensor, lengths: List[int], init_latents: Optional[torch.Tensor] = None, seed: Optional[int] = None,
-               first_index: int = 0):
+               first_index: int = 0, return_trajectory: bool = False):
         """text_emb [2B, 1, 768] (uncond half first) -> (joints [B,T,22,3], feats [B,T,nfeats], latents [B,1,D]) on device.
         eta > 0: the step noise of motion m is the engine's Philox stream keyed (seed, first_index + m); `seed` None = drawn from torch's
-        generator."""
+        generator.  return_trajectory: a fourth result, the latents after every scheduler step [steps, B, D] (mldhip_sample_many_traj; its last
+        row is `latents`)."""
         lengths = [int(x) for x in lengths]
         B, T = len(lengths), max(lengths)
         dev = text_emb.device
@@ -152,6 +153,12 @@ class MLD(nn.Module):
         feats = torch.empty(B, T, self.nfeats, device=dev)
         joints = torch.empty(B, T, self.njoints, 3, device=dev)
         seed = self._noise_seed(seed)
+        if return_trajectory:
+            traj = self._traj_buffer(eng, B, dev)
+            eng.sample_many_traj([dict(text_emb=text_emb, init_latents=init_latents, lengths=lengths, latents_out=lat, feats_out=feats,
+                                       joints_out=joints, traj_out=traj)], None if seed is None else [(seed, int(first_index))],
+                                 _engine.current_stream_handle(text_emb))
+            return joints, feats, lat, traj
         if seed is None:
             eng.sample(text_emb, init_latents, lengths, lat, feats, joints, _engine.current_stream_handle(text_emb))
         else:
@@ -160,14 +167,18 @@ class MLD(nn.Module):
         return joints, feats, lat
 
     @torch.no_grad()
-    def sample_many(self, requests, init_latents=None, pipeline: bool = False, seed: Optional[int] = None, first_index: int = 0):
+    def sample_many(self, requests, init_latents=None, pipeline: bool = False, seed: Optional[int] = None, first_index: int = 0,
+                    return_trajectory: bool = False):
         """Several independent text-to-motion requests as ONE engine call (``mldhip_sample_many``: one reverse-diffusion chain +
         one decode over all of them; the engine needs ``max_batch >= total motions``).  `requests` = [(text_emb [2B_i,1,768],
         lengths_i), ...]; returns [(joints_i, feats_i, latents_i), ...] on device, each shaped as ``sample`` would return it.
 
         ``pipeline=True`` (engine option "many_pipeline"; ``mld_hip.engine.configure("text", max_in_flight=2)`` before the first use): the
         requests run ONE AFTER THE OTHER -- the reference's own loop, batch after batch (mld.py:618-672) -- each exactly what ``sample`` returns
-        for it, with the decode of request k overlapped with the reverse loop of request k + 1 (bs-64 requests: 7.0 instead of 8.0 ms each)."""
+        for it, with the decode of request k overlapped with the reverse loop of request k + 1 (bs-64 requests: 7.0 instead of 8.0 ms each).
+
+        ``return_trajectory=True``: every result tuple gets a fourth entry, the request's latents after every scheduler step [steps, B_i, D]
+        (mldhip_sample_many_traj; such a call runs as one chain, also with ``pipeline=True``)."""
         if self.vae_type == "no" or self.condition == "action":
             raise NotImplementedError("sample_many serves the text-to-motion latent model")
         eng = self._engine()
@@ -189,12 +200,18 @@ class MLD(nn.Module):
             joints = torch.empty(B, T, self.njoints, 3, device=dev)
             keep.append((text_emb, lat0))
             reqs.append(dict(text_emb=text_emb, init_latents=lat0, lengths=lengths, latents_out=lat, feats_out=feats, joints_out=joints))
+            if return_trajectory:
+                reqs[-1]["traj_out"] = self._traj_buffer(eng, B, dev)
+                outs.append((joints, feats, lat, reqs[-1]["traj_out"]))
+                continue
             outs.append((joints, feats, lat))
         if pipeline:
             eng.set_option("many_pipeline", 1)
         seed = self._noise_seed(seed)
         try:
-            if seed is None:
+            if return_trajectory:
+                eng.sample_many_traj(reqs, None if seed is None else self._keys(seed, reqs, first_index), stream)
+            elif seed is None:
                 eng.sample_many(reqs, stream)
             else:       # motion k of request i is motion sum(B_<i) + k of the call: the same noise however the call is split
                 eng.sample_many_seeded(reqs, self._keys(seed, reqs, first_index), stream)
@@ -202,6 +219,10 @@ class MLD(nn.Module):
             if pipeline:
                 eng.set_option("many_pipeline", 0)
         return outs
+
+    def _traj_buffer(self, eng, B: int, dev) -> torch.Tensor:
+        """[steps, B, latent_size * D]: what mldhip_sample_many_traj fills for a request of B motions (the shape the reference's torch.cat gives)"""
+        return torch.empty(int(eng.cfg.num_inference_steps), B, self.latent_dim[0] * self.latent_dim[-1], device=dev, dtype=torch.float)
 
     @staticmethod
     def _keys(seed: int, reqs, first_index: int = 0):
@@ -241,8 +262,9 @@ class MLD(nn.Module):
 
     @torch.no_grad()
     def sample_action(self, actions, lengths: List[int], init_latents: Optional[torch.Tensor] = None, device=None, seed: Optional[int] = None,
-                      first_index: int = 0):
-        """Action labels [B] / [B, 1] -> (feats [B, T, nfeats], latents [B, 1, D]) on device: ONE mldhip_sample_action call."""
+                      first_index: int = 0, return_trajectory: bool = False):
+        """Action labels [B] / [B, 1] -> (feats [B, T, nfeats], latents [B, 1, D]) on device: ONE mldhip_sample_action call.
+        return_trajectory: a third result, the latents after every scheduler step [steps, B, D] (mldhip_sample_many_traj)."""
         lengths = [int(x) for x in lengths]
         acts = [int(a) for a in (actions.reshape(-1).tolist() if torch.is_tensor(actions) else list(actions))]
         B, T = len(lengths), max(lengths)
@@ -254,6 +276,11 @@ class MLD(nn.Module):
         lat = torch.empty(B, self.latent_dim[0], self.latent_dim[-1], device=dev)
         feats = torch.empty(B, T, self.nfeats, device=dev)
         seed = self._noise_seed(seed)
+        if return_trajectory:
+            traj = self._traj_buffer(eng, B, dev)
+            eng.sample_many_traj([dict(actions=acts, init_latents=init_latents, lengths=lengths, latents_out=lat, feats_out=feats, traj_out=traj)],
+                                 None if seed is None else [(seed, int(first_index))], _engine.current_stream_handle(init_latents))
+            return feats, lat, traj
         if seed is None:
             eng.sample_action(acts, init_latents, lengths, lat, feats, _engine.current_stream_handle(init_latents))
         else:
@@ -351,9 +378,9 @@ class MLD(nn.Module):
 
     @torch.no_grad()
     def _diffusion_reverse(self, encoder_hidden_states, lengths=None, init_latents: Optional[torch.Tensor] = None,
-                           step_noise: Optional[torch.Tensor] = None):
+                           step_noise: Optional[torch.Tensor] = None, trace: Optional[list] = None):
         """The reference's Python loop (mld.py:290-360) over the drop-in parts -> [latent_size, B, D]
-        ([T, B, nfeats] for vae_type 'no')."""
+        ([T, B, nfeats] for vae_type 'no').  `trace`: a list that receives prev_sample of every step, permuted like the result (mld.py:418-421)."""
         bsz = encoder_hidden_states.shape[0] // (2 if self.do_classifier_free_guidance else 1)
         dev = init_latents.device if init_latents is not None else encoder_hidden_states.device
         if self.vae_type == "no":
@@ -380,4 +407,36 @@ class MLD(nn.Module):
                 u, c = noise_pred.chunk(2)
                 noise_pred = u + self.guidance_scale * (c - u)
             latents = self.scheduler.step(noise_pred, t, latents, **extra).prev_sample
+            if trace is not None:
+                trace.append(latents.permute(1, 0, 2))
         return latents.permute(1, 0, 2)
+
+    @torch.no_grad()
+    def _diffusion_reverse_tsne(self, encoder_hidden_states, lengths=None, init_latents: Optional[torch.Tensor] = None, seed: Optional[int] = None):
+        """mld.py:362-424: the reverse loop that keeps the latents after every scheduler step -> [steps, B, D], the shape the reference's
+        torch.cat gives for latent_size 1 (what its denoising-process figures and t-SNE plots read).  Fused latent models: ONE
+        mldhip_sample_many_traj call -- the trajectory of the loop that serves sampling, not of a different one; otherwise (a swapped part, the
+        diffusion-only variant) the modular Python loop, collecting prev_sample per step.  `lengths` is only needed by the diffusion-only variant,
+        as in the reference; eta > 0: `seed` keys the fused path's Philox stream (None = drawn from torch's generator)."""
+        if not self.fused or self.vae_type == "no":
+            steps: list = []
+            self._diffusion_reverse(encoder_hidden_states, lengths, init_latents, trace=steps)
+            return torch.cat(steps)
+        bsz = encoder_hidden_states.shape[0] // 2
+        lengths = [int(x) for x in lengths] if lengths is not None else [1] * bsz      # (the latent loop has no masks: the lengths only size a decode nobody asks for)
+        dev = init_latents.device if init_latents is not None else encoder_hidden_states.device
+        if init_latents is None:
+            init_latents = torch.randn((bsz, self.latent_dim[0], self.latent_dim[-1]), device=dev, dtype=torch.float)
+        init_latents = init_latents.float().contiguous()
+        eng = self._engine()
+        stream = _engine.current_stream_handle(init_latents)
+        _engine.finalize_if_dirty(eng, stream)
+        traj = self._traj_buffer(eng, bsz, dev)
+        req = dict(init_latents=init_latents, lengths=lengths, traj_out=traj)
+        if self.condition == "action":
+            req["actions"] = [int(a) for a in encoder_hidden_states.reshape(-1).tolist()[bsz:]]      # cond = cat(zeros_like(actions), actions) (mld.py:716-717)
+        else:
+            req["text_emb"] = encoder_hidden_states.float().contiguous()
+        seed = self._noise_seed(seed)
+        eng.sample_many_traj([req], None if seed is None else [(seed, 0)], stream)
+        return traj
