@@ -48,9 +48,6 @@ struct FfnArgs {
 };
 
 
-#ifndef TB_EXP
-#define TB_EXP 0          // tools/loopbench/tail_bench.hip experiments (measurement only, 0 in the library)
-#endif
 constexpr int kFsXs = 264, kFsHs = 136;      // row strides (words), = 8 mod 16 (conflict-free fragment reads)
 template <int RT>
 constexpr int ffn_strip_lds_bytes() { return (RT * 16 * kFsXs + RT * 16 * kFsHs + 2 * 8 * RT * 16 + RT * 16) * 4; }   // RT = 6: 160 128 B; RT = 4: 106 752 B; RT = 3: 80 064 B (two per CU)

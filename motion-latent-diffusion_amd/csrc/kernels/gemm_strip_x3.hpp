@@ -28,9 +28,6 @@ struct StripGemmArgs {
   const float* g2 = nullptr; const float* b2 = nullptr;
 };
 
-#ifndef SB_EXP
-#define SB_EXP 0          // tools/loopbench/strip_bench.hip experiments (measurement only, 0 in the library)
-#endif
 template <int RT, int NSEG, bool STAGE>
 constexpr int strip_gemm_lds_bytes() { return (NSEG * RT * 16 * kFsXs + (STAGE ? RT * 16 * kFsHs : 0) + 2 * 8 * RT * 16 + RT * 16) * 4; }
 
@@ -45,10 +42,9 @@ constexpr int strip_gemm_lds_bytes() { return (NSEG * RT * 16 * kFsXs + (STAGE ?
 template <int RT, int NSEG, bool LN, bool STAGE, bool NT = false>
 __global__ __launch_bounds__(512, (RT * NSEG <= 4 && RT <= 3 ? 4 : 2)) void strip_gemm_x3_kernel(StripGemmArgs p) {      // RT <= 3: 80 KB of LDS and 128 registers -- two workgroups per CU
   static_assert(!(LN && (NSEG != 1 || STAGE)), "the LayerNorm form is the N = 256, K = 256 out-projection");
-#ifndef SB_RING3
-#define SB_RING3 4        // items in flight per lane of the 48-row form (128 registers: 8 spill 40 B)
-#endif
-  constexpr int RING = LN ? 4 : (RT <= 3 ? SB_RING3 : 8);   // (RT <= 3 with one K segment, RT = 2 with two: the forms at four waves per SIMD)      // weight items in flight per lane
+  // weight items in flight per lane (the note above); the forms at four waves per SIMD -- RT <= 3 with one K segment, RT = 2 with two -- hold 4:
+  // at their 128 registers a ring of 8 spills 40 B
+  constexpr int RING = LN ? 4 : (RT <= 3 ? 4 : 8);
   constexpr int BM = RT * 16, XS = kFsXs, HS = kFsHs;
 #if defined(MLDHIP_SIM)
   float* smem = reinterpret_cast<float*>(hipsim::blk().dyn_smem.data());
@@ -89,14 +85,13 @@ __global__ __launch_bounds__(512, (RT * NSEG <= 4 && RT <= 3 ? 4 : 2)) void stri
   auto mma_item = [&](int j, const F4 (&x)[RT][2], f32x4 (&acc)[RT]) __attribute__((always_inline)) {
     const int slot = j % RING;
     const U4 wh = __builtin_bit_cast(U4, ring[slot][0]), wl = __builtin_bit_cast(U4, ring[slot][1]);
-    if (SB_EXP & 8) { acc[0][0] += ring[slot][0].x + ring[slot][1].w + x[0][0].x; gload(slot); sched_fence(); return; }
 #pragma unroll
     for (int t = 0; t < RT; ++t) acc[t] = mfma_x3_16x16x32(__builtin_bit_cast(U4, x[t][1]), wh, acc[t]);
 #pragma unroll
     for (int t = 0; t < RT; ++t) acc[t] = mfma_x3_16x16x32(__builtin_bit_cast(U4, x[t][0]), wl, acc[t]);
 #pragma unroll
     for (int t = 0; t < RT; ++t) acc[t] = mfma_x3_16x16x32(__builtin_bit_cast(U4, x[t][0]), wh, acc[t]);
-    if (!(SB_EXP & 4)) gload(slot);
+    gload(slot);
     sched_fence();
   };
 
@@ -111,7 +106,7 @@ __global__ __launch_bounds__(512, (RT * NSEG <= 4 && RT <= 3 ? 4 : 2)) void stri
       const int idx = tid + j * 512, row = idx >> 6, c4 = idx & 63;
       int m = m0 + row;
       m = m < p.M ? m : p.M - 1;
-      const F4 v = (SB_EXP & 1) ? F4{0.01f * c4, 0.5f, -0.25f, 0.001f * row} : ld4_hint<NT>(src + (size_t)m * 256 + c4 * 4);
+      const F4 v = ld4_hint<NT>(src + (size_t)m * 256 + c4 * 4);
       unsigned h0, l0, h1, l1;
       split16_pair(v.x, v.y, h0, l0);
       split16_pair(v.z, v.w, h1, l1);
@@ -152,7 +147,7 @@ __global__ __launch_bounds__(512, (RT * NSEG <= 4 && RT <= 3 ? 4 : 2)) void stri
 #pragma unroll
           for (int j = 0; j < RT; ++j) {
             const int idx = tid + j * 512, row = idx >> 5, c4 = idx & 31;
-            if (m0 + row < p.M && (!(SB_EXP & 2) || row == 0)) st4_hint<NT>(p.Y + (size_t)(m0 + row) * p.ldy + pr * 256 + cb * 128 + c4 * 4, ld4(St + row * HS + c4 * 4));
+            if (m0 + row < p.M) st4_hint<NT>(p.Y + (size_t)(m0 + row) * p.ldy + pr * 256 + cb * 128 + c4 * 4, ld4(St + row * HS + c4 * 4));
           }
         }
       } else {
@@ -169,7 +164,7 @@ __global__ __launch_bounds__(512, (RT * NSEG <= 4 && RT <= 3 ? 4 : 2)) void stri
 #pragma unroll
         for (int j = 0; j < RT * 2; ++j) {
           const int idx = tid + j * 512, row = idx >> 6, c4 = idx & 63;
-          if (m0 + row < p.M && (!(SB_EXP & 2) || row == 0)) st4_hint<NT>(p.Y + (size_t)(m0 + row) * p.ldy + c4 * 4, ld4(Xs + row * XS + c4 * 4));
+          if (m0 + row < p.M) st4_hint<NT>(p.Y + (size_t)(m0 + row) * p.ldy + c4 * 4, ld4(Xs + row * XS + c4 * 4));
         }
       }
     } else {

@@ -7,6 +7,11 @@
 #include <cstdlib>
 #include <random>
 #include <vector>
+#include "attention.hpp"   // the library's include order (mldhip.hip) up to novae.hpp: loop_fused.hpp takes NoiseKey and latent_noise4 from it
+#include "elementwise.hpp"
+#include "gemm.hpp"
+#include "gemm_pipe.hpp"
+#include "novae.hpp"
 #include "gemm_strip_x3.hpp"
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e_)); return 1; } } while (0)
 using namespace mld;

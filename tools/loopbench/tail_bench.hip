@@ -7,6 +7,11 @@
 #include <cstdlib>
 #include <random>
 #include <vector>
+#include "attention.hpp"   // the library's include order (mldhip.hip) up to novae.hpp: loop_fused.hpp takes NoiseKey and latent_noise4 from it
+#include "elementwise.hpp"
+#include "gemm.hpp"
+#include "gemm_pipe.hpp"
+#include "novae.hpp"
 #include "ffn_strip.hpp"
 
 #ifndef TB_VARIANT
