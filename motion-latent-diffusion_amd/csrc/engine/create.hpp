@@ -173,7 +173,7 @@ void carve_latent(E* e, Carver& want) {
   const size_t KP = (NF + 31) / 32 * 32;                 // feature width padded to the MFMA K chunk
   want(&e->X0, rows * D); want(&e->Ha, rows * D); want(&e->Hb, rows * D); want(&e->H1, rows * D); want(&e->LNO, rows * D);
   for (int i = 0; i < 8; ++i) want(&e->S[i], (i < (int)(L - 1) / 2) ? rows * D : 0);
-  want(&e->QKV, rows * 3 * D); want(&e->AO, rows * D); want(&e->FF, rows * F);
+  want(&e->QKV, rows * 3 * D); want(&e->AO, rows * D); want(&e->FF, rows * std::max(F, KP));   // FF: the FFN hidden rows, and encode_body's padded features [B*T][KP]
   want(&e->lat, Bm * D); want(&e->zbuf, Bm * D);
   want(&e->FS, (Bm + 7) / 8 * ((L - 1) / 2) * 48 * D);
   {
