@@ -78,14 +78,16 @@ enum {                     /* arithmetic mode of the matrix kernels.  In EVERY m
  * scheduler}.yaml that the hot path consumes.
  *
  * Which fields select which kernels.  mldhip_create accepts a family of models (num_layers odd 3..17, or 1..24 for the diffusion-only variant;
- * ff_size 256 / 512 / 1024; text_dim a multiple of 32; nfeats 67..1024; any guidance_scale; any num_inference_steps that divides num_train_timesteps;
+ * ff_size 256 / 512 / 1024; text_dim a multiple of 32; nfeats up to 1024; on MldVae and diffusion-only handles a skeleton of 1 <= njoints <= 64 joints with
+ * nfeats >= 4 + 3 (njoints - 1), the columns recover_from_ric reads -- HumanML3D 22 / 263, KIT-ML 21 / 251 -- while ActorVae handles take any njoints: their joints need SMPL; any guidance_scale; any num_inference_steps that divides num_train_timesteps;
  * steps_offset, set_alpha_to_one, beta_start, beta_end; nclasses 1..4096 and vae_num_layers 0..17 on action engines), but only some of them get every
  * kernel family:
  *   - the persistent loop ("loop_kernel" 3), the cluster loop ("loop_kernel" 4), the weight streams and the row-strip decoder / encoder kernels
  *     ("ffn_strip", "dec_tail", "dec_lean") are built for latent_dim 256, ff_size 1024, 4 heads only.  With ff_size 256 or 512 the reverse loop runs on the
  *     latency or column-split kernels at every batch size ("loop_kernel" 3 and 4 are refused) and the decoder / encoder layers on the staged GEMMs;
- *   - the one-launch final stage of the decoder (final norm + final_layer, and its joints-only form) is built for 256 < nfeats <= 264 only; every other
- *     width ends in a row LayerNorm and a GEMM with a ragged N.  The encoder pads the features to a multiple of 32 columns;
+ *   - the one-launch final stage of the decoder (final norm + final_layer, and its joints-only form where 4 + 3 (njoints - 1) <= 128) is built for
+ *     256 < nfeats <= 264 (three column blocks: HumanML3D) and for 128 < nfeats < 256 (two column blocks: KIT-ML); every other width, 128 and 256
+ *     included, ends in a row LayerNorm and a staged GEMM.  The encoder pads the features to a multiple of 32 columns;
  *   - guidance_scale <= 1 runs the same kernels with guidance 1.0 (the conditional half of the [2B] batch, which the entry points still take); on an
  *     action engine mldhip_denoiser_forward_action then gives no row the zero embedding.
  * All of them compute the same model.  The whole accepted envelope is tested against a float64 reference, on the MI355X and on the functional simulator
@@ -97,8 +99,8 @@ typedef struct mldhip_config {
   int32_t ff_size;              /* 1024 */
   int32_t num_layers;           /* 9 (odd: SkipTransformer, cross_attention.py:26) */
   int32_t num_heads;            /* 4 */
-  int32_t nfeats;               /* DATASET.NFEATS = 263 */
-  int32_t njoints;              /* 22 */
+  int32_t nfeats;               /* DATASET.NFEATS = 263 (KIT-ML: 251) */
+  int32_t njoints;              /* DATASET.NJOINTS = 22 (KIT-ML: 21); MldVae / diffusion-only: 1..64 with nfeats >= 4 + 3 (njoints - 1) */
   int32_t text_dim;             /* denoiser.params.text_encoded_dim = 768 */
   int32_t max_batch;            /* capacity: motions per sample() call */
   int32_t max_frames;           /* capacity: frames per motion (<= 288 in this release) */

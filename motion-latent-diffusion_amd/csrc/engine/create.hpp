@@ -107,7 +107,9 @@ const char* config_error(const mldhip_config* cfg) {
   if (cfg->condition != MLDHIP_COND_TEXT && cfg->condition != MLDHIP_COND_ACTION) return "condition must be text or action";
   if (cfg->condition == MLDHIP_COND_ACTION && (cfg->nclasses < 1 || cfg->nclasses > 4096)) return "action condition needs 1 <= nclasses <= 4096";
   if (cfg->vae_num_layers < 0 || cfg->vae_num_layers > 17) return "vae_num_layers must be 0..17";
-  if (cfg->vae_arch != MLDHIP_VAE_ACTOR && (cfg->nfeats < 67 || cfg->njoints != 22)) return "HumanML3D layout expected: nfeats >= 67, njoints 22";
+  // MldVae / diffusion-only: joints by recover_from_ric, which reads feature columns 0 .. 4 + 3 (njoints - 1) - 1 (HumanML3D: 22 joints, 263 features; KIT-ML: 21, 251)
+  if (cfg->vae_arch != MLDHIP_VAE_ACTOR && (cfg->njoints < 1 || cfg->njoints > 64 || cfg->nfeats < 4 + 3 * (cfg->njoints - 1)))
+    return "skeleton: 1 <= njoints <= 64 and nfeats >= 4 + 3 (njoints - 1), the feature columns feats2joints reads (HumanML3D 22 / 263, KIT-ML 21 / 251)";
   if (cfg->nfeats < 1 || cfg->nfeats > 1024) return "nfeats must be 1..1024";
   if (cfg->num_inference_steps < 1 || cfg->num_train_timesteps % cfg->num_inference_steps) return "num_train_timesteps must be a multiple of num_inference_steps";
   if (cfg->scheduler_type == MLDHIP_SCHED_DDIM &&
@@ -234,6 +236,7 @@ void register_dynamic_lds() {
   (void)hipFuncSetAttribute((const void*)ffn_strip_x3_kernel<3, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ffn_strip_lds_bytes<3>());
   (void)hipFuncSetAttribute((const void*)dec_tail_l0_x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ffn_strip_lds_bytes<3>());
   (void)hipFuncSetAttribute((const void*)final_strip_x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, final_strip_lds_bytes());
+  (void)hipFuncSetAttribute((const void*)final_strip2_x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, final_strip_lds_bytes());
   (void)hipFuncSetAttribute((const void*)final_joints_x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, final_strip_lds_bytes());
   (void)hipFuncSetAttribute((const void*)attn_flash_x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kFlashLdsBytes);
   (void)hipFuncSetAttribute((const void*)attn_flash_h_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kFlashHLdsBytes);

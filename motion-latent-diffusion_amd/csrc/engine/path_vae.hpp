@@ -204,7 +204,7 @@ void skip_linear(Ctx& c, const std::string& prefix, int i, const float* x, const
 }
 
 // MldVae.decode (mld_vae.py:186-248).  z [B, D]; lens_dev already holds the lengths.
-// joints_only: nobody reads the features but feats2joints -- feats_out then receives [M][joints_pitch] rows (columns 0 .. 66 + padding) where the
+// joints_only: nobody reads the features but feats2joints -- feats_out then receives [M][joints_pitch] rows (columns 0 .. joint_feat_cols - 1 + padding) where the
 // joints-only final stage is built ("dec_lean"; *joints_pitch says which layout was written)
 void decode_body(Ctx& c, const float* z, int B, int T, float* feats_out, bool joints_only = false, int* joints_pitch = nullptr) {
   E* e = c.e;
@@ -259,13 +259,14 @@ void decode_body(Ctx& c, const float* z, int B, int T, float* feats_out, bool jo
     a.X = e->Ha; a.gamma = P(e, "vae.decoder.norm.weight"); a.beta = P(e, "vae.decoder.norm.bias"); a.W = e->final_stream;
     a.bias = P(e, "vae.final_layer.bias"); a.Y = feats_out; a.M = M; a.NF = NF; a.lens = e->lens_dev; a.rpg = T;
     if (joints_only && e->dec_lean && e->final_joints_stream) {
-      // block 0 alone, rows of (67 + 1 pad) floats: the same chunk order and split products per column as the full kernel -> the same bits
+      // block 0 alone, rows of joint_feat_cols rounded up to 4 floats (HumanML3D: 67 + 1 pad, KIT-ML: 64): the same chunk order and split products per column as the full kernel -> the same bits
       a.W = e->final_joints_stream; a.NV = joint_feat_cols(e); a.NF = (a.NV + 3) / 4 * 4;
       if (joints_pitch) *joints_pitch = a.NF;
       MLD_COUNTED(c, "final_joints_x3", MLD_LAUNCH(final_joints_x3_kernel, dim3((M + kFinalStripRows - 1) / kFinalStripRows), dim3(512), final_strip_lds_bytes(), c.stream, a));
       return;
     }
-    MLD_COUNTED(c, "final_strip_x3", MLD_LAUNCH(final_strip_x3_kernel, dim3((M + kFinalStripRows - 1) / kFinalStripRows), dim3(512), final_strip_lds_bytes(), c.stream, a));
+    if (final_strip_blocks(e) == 2) MLD_COUNTED(c, "final_strip2_x3", MLD_LAUNCH(final_strip2_x3_kernel, dim3((M + kFinalStripRows - 1) / kFinalStripRows), dim3(512), final_strip_lds_bytes(), c.stream, a));
+    else MLD_COUNTED(c, "final_strip_x3", MLD_LAUNCH(final_strip_x3_kernel, dim3((M + kFinalStripRows - 1) / kFinalStripRows), dim3(512), final_strip_lds_bytes(), c.stream, a));
     return;
   }
   MLD_COUNTED(c, "layernorm_rows", MLD_LAUNCH(layernorm_rows_kernel, dim3((M + 3) / 4), dim3(256), 0, c.stream, e->Ha, e->LNO, P(e, "vae.decoder.norm.weight"), P(e, "vae.decoder.norm.bias"), M));

@@ -77,8 +77,8 @@ struct mldhip_engine {
   std::vector<Param> params;
   std::map<std::string, int> index;
   float* arena = nullptr;
-  const float* final_stream = nullptr;   // split modes, MldVae: vae.final_layer.weight zero-padded to 384 rows as a fragment-ordered stream (kernels/final_strip.hpp); inside ffn_streams
-  const float* final_joints_stream = nullptr;   // ... rows 0 .. 66 of it (what feats2joints reads) zero-padded to ONE 128-row block: the joints-only final stage (final_joints_x3_kernel, "dec_lean"); inside ffn_streams
+  const float* final_stream = nullptr;   // split modes, MldVae: vae.final_layer.weight zero-padded to three (256 < nfeats <= 264) or two (128 < nfeats < 256) 128-row blocks as a fragment-ordered stream (kernels/final_strip.hpp); inside ffn_streams
+  const float* final_joints_stream = nullptr;   // ... rows 0 .. joint_feat_cols - 1 of it (what feats2joints reads: 67 on HumanML3D, 64 on KIT-ML) zero-padded to ONE 128-row block: the joints-only final stage (final_joints_x3_kernel, "dec_lean"); inside ffn_streams
   float* ffn_streams = nullptr;   // split modes: linear1 / linear2 of every decoder / encoder layer as fragment-ordered item streams (kernels/ffn_strip.hpp)
   std::map<const float*, const float*> ffn_stream_of;   // linear1.weight (arena pointer) -> its layer's stream
   std::map<const float*, const float*> gemm_stream_of;  // in_proj / out_proj / skip-linear weight -> its stream (kernels/gemm_strip_x3.hpp)
@@ -166,7 +166,7 @@ struct mldhip_engine {
   int ffn_strip = 1;         // "ffn_strip": register-direct decoder kernels (ffn_strip.hpp, gemm_strip_x3.hpp): 0 off, 1 auto strip height, 4 / 6 = 64 / 96 rows always
   int dec_tail = 1;          // "dec_tail": out-projection + norms + feed-forward block of a decoder layer as one launch (chip-filling launches, split modes)
   int dec_l0_once = 1;       // "dec_l0_once": decoder layer 0 projects its input -- the positional rows, the same for every sample -- once per call ([T] rows instead of [B T])
-  int dec_lean = 1;          // "dec_lean": the decoder skips what the joints never read -- a call nobody asks features of ends in the 67-column final stage (final_joints_x3_kernel, [M][68] staging rows), layer 0 reads its residual from the positional table and its attention output from one representative sample per distinct length (no init_queries pass, non-representative attention workgroups return at once), feats2joints counts the non-finite joints as it stores them; bit-identical results.  0 = the full feature row, per-sample layer 0 and the separate counting pass
+  int dec_lean = 1;          // "dec_lean": the decoder skips what the joints never read -- a call nobody asks features of ends in the final stage of the columns the joints read (final_joints_x3_kernel: 67 columns in [M][68] staging rows on HumanML3D, 64 in [M][64] on KIT-ML), layer 0 reads its residual from the positional table and its attention output from one representative sample per distinct length (no init_queries pass, non-representative attention workgroups return at once), feats2joints counts the non-finite joints as it stores them; bit-identical results.  0 = the full feature row, per-sample layer 0 and the separate counting pass
   int dec_half = 0;          // "dec_half": OPT-IN (default 0 = fp32 Q | K | V and split x3 products: gemm_strip_x3.hpp, attention.hpp).  1 / 4 / 6: split mode, decoder self-attention block on half Q | K | V (kernels/dec_half.hpp): in-projection with half activation rows x split weights (2 matrix instructions per product), Q | K | V stored as halves, attention on plain half operands -- kept only where finalize's probe reads it below MLDHIP_PROBE_TOL_HALF on the handle's weights; 2 = without that veto (A/B tools).  Off by default because it is not safe in general: profiles/r06_decoder_precision.json (heavy-tailed weights on O(1) latents: 6.7e-4 .. 8.8e-4 on the joints)
   int tile_x3 = 1;           // "tile_x3": split-f16 mode runs the latency kernels (tile32.hpp) on split-f16 MFMAs too (0: exact fp32)
   int strip_gemm = 1;        // "strip_gemm": split modes, decoder / encoder in-projection, out-projection (+ LayerNorms) and skip linears on the row-strip kernels (kernels/gemm_strip_x3.hpp); 0 = the staged 64 x 128 / 64 x 256 tiles

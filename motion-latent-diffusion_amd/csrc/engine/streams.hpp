@@ -171,6 +171,14 @@ int build_cluster_stream(Ctx& c) {
 // feature columns feats2joints_kernel reads: 0 .. 3 (root) and 4 + 3 (j - 1) + {0, 1, 2} for the other joints -- 67 on HumanML3D
 int joint_feat_cols(const E* e) { return 4 + 3 * (e->cfg.njoints - 1); }
 
+// 128-column blocks of the one-launch final stage of MldVae.decode (kernels/final_strip.hpp), 0 = the width has none: 3 for 256 < nfeats <= 264,
+// 2 for 128 < nfeats < 256; 128 and 256 themselves are whole staged tiles and stay on the staged GEMM
+int final_strip_blocks(const E* e) {
+  const int NF = e->cfg.nfeats;
+  if (is_actor(e) || is_novae(e)) return 0;
+  return NF > 256 && NF <= kFsXs ? 3 : NF > 128 && NF < 256 ? 2 : 0;
+}
+
 // finalize-time (split precision modes): linear1 / linear2 of every decoder / encoder layer in the item order of
 // kernels/ffn_strip.hpp -- run1(0), then [run1(hb), run2(hb - 1)] for hb = 1..7, then run2(7) -- as split-f16 fragment images
 int build_ffn_streams(Ctx& c) {
@@ -207,13 +215,14 @@ int build_ffn_streams(Ctx& c) {
     if (!is_actor(e)) for (int i = 0; i < nbv; ++i) gstream(P(e, "vae.encoder.linear_blocks." + std::to_string(i) + ".weight"), 256, 512);
   }
   // kernels/final_strip.hpp: vae.final_layer.weight [NF][256], 256 < NF <= 264 (the strip's 48 x NF results are parked in its 48 x 264-word image),
-  // zero-padded to three 128-row blocks: per chunk [block 0, 1, 2]; pad = valid rows of the block (pack_stream_rows_kernel zero-fills the rest)
+  // zero-padded to three 128-row blocks: per chunk [block 0, 1, 2]; pad = valid rows of the block (pack_stream_rows_kernel zero-fills the rest).
+  // 128 < NF < 256 (KIT-ML: 251): two blocks, per chunk [block 0, 1] (final_strip2_x3_kernel)
   const size_t final_first = items.size();
-  const int NFv = e->cfg.nfeats;
-  if (e->group_ready[1] && !is_actor(e) && NFv > 256 && NFv <= kFsXs) {
+  const int NFv = e->cfg.nfeats, final_blocks = final_strip_blocks(e);
+  if (e->group_ready[1] && final_blocks) {
     const float* wf = P(e, "vae.final_layer.weight");
     for (int kc = 0; kc < 8; ++kc)
-      for (int blk = 0; blk < 3; ++blk) items.push(wf, 256, blk * 128, kc * 32, std::min(128, NFv - blk * 128));
+      for (int blk = 0; blk < final_blocks; ++blk) items.push(wf, 256, blk * 128, kc * 32, std::min(128, NFv - blk * 128));
   }
   // ... and block 0 cut to the rows feats2joints reads (joint_feat_cols), per chunk: the joints-only final stage (final_joints_x3_kernel)
   const size_t joints_first = items.size();

@@ -9,6 +9,12 @@
 // chunk feed three items), parks the 48 x NF results in the image's own rows and writes them out as ONE contiguous block of 48 NF
 // floats with 16-byte stores (rows of the output are NF floats apart: a strip of rows is contiguous; 48 NF x 4 bytes is a multiple
 // of 16 for every NF).  HBM traffic: the input once, the output once.
+//
+// Two-block form (final_strip2_x3_kernel) for 128 < NF < 256 (KIT-ML: 251 = 12 x 21 - 1): the weight zero-padded to two 128-row blocks, the stream
+// [chunk][block 0, block 1] = 16 items, everything else as above (48 x NF <= 48 x 255 results fit the image).  The range is open at both ends on purpose:
+// NF = 256 has no ragged edge -- the staged GEMM runs it as two full 128-column tiles with 16-byte stores, the case the staged path is built for -- and
+// NF <= 128 is a single tile there, which re-reads nothing; both widths stay on layernorm_rows_kernel + the staged GEMM, and their launch counts are what
+// the configuration-envelope tests pin.
 #pragma once
 #include "gemm_strip_x3.hpp"
 
@@ -17,7 +23,7 @@ namespace mld {
 struct FinalStripArgs {
   const float* X = nullptr;          // [M][256] decoder output before decoder.norm
   const float* gamma = nullptr; const float* beta = nullptr;     // decoder.norm
-  const float* W = nullptr;          // fragment-ordered stream of the weight padded to 384 rows: 8 chunks x [block 0, block 1, block 2]
+  const float* W = nullptr;          // fragment-ordered stream of the weight padded to NB x 128 rows: 8 chunks x [block 0, .., block NB - 1]
   const float* bias = nullptr;       // [NF]
   float* Y = nullptr;                // [M][NF]
   int M = 0, NF = 0;
@@ -48,7 +54,7 @@ __global__ __launch_bounds__(512) void pack_stream_rows_kernel(const float* __re
   *reinterpret_cast<U4*>(dst + 4) = lo;
 }
 
-// NB = column blocks of 128: 3 = the whole feature row (final_strip_x3_kernel), 1 = block 0 alone (final_joints_x3_kernel: the stream holds
+// NB = column blocks of 128: 3 / 2 = the whole feature row (final_strip_x3_kernel: 256 < NF <= 264, final_strip2_x3_kernel: 128 < NF < 256), 1 = block 0 alone (final_joints_x3_kernel: the stream holds
 // [chunk][block 0] only).  A column's accumulator sees the same products in the same order in both: columns of block 0 agree to the bit.
 template <int NB>
 __device__ __forceinline__ void final_strip_body(const FinalStripArgs& p) {
@@ -154,7 +160,7 @@ __device__ __forceinline__ void final_strip_body(const FinalStripArgs& p) {
   for (int b = 0; b < NB; ++b) {
     const int col = b * 128 + col0;
     float bi;
-    if constexpr (NB == 3) bi = p.bias[col < p.NF ? col : p.NF - 1];
+    if constexpr (NB >= 2) bi = p.bias[col < p.NF ? col : p.NF - 1];      // the last block is ragged: its pad columns read a valid entry and store nothing
     else bi = col < p.NV ? p.bias[col] : 0.f;            // pad columns NV .. NF - 1: zero weight rows, no bias -> zeros
     if (col < p.NF) {
 #pragma unroll
@@ -183,9 +189,13 @@ __device__ __forceinline__ void final_strip_body(const FinalStripArgs& p) {
 // grid = ceil(M / 48); block = 512
 __global__ __launch_bounds__(512, 4) void final_strip_x3_kernel(FinalStripArgs p) { final_strip_body<3>(p); }
 
+// 128 < NF < 256: two column blocks (a name of its own, not a template argument: tools and tests look kernels up by substring)
+__global__ __launch_bounds__(512, 4) void final_strip2_x3_kernel(FinalStripArgs p) { final_strip_body<2>(p); }
+
 // The joints-only end of the decoder ("dec_lean"): feats2joints reads feature columns 0 .. 66 and nothing else, so a call nobody asks features
 // of multiplies block 0 alone (rows 0 .. NV - 1 of the weight, zero-padded to 128: a third of the matrix instructions) and writes [M][NF = 68]
 // staging rows (NV = 67 columns + one pad: rows stay 16-byte aligned; a quarter of the store), which feats2joints_kernel reads with 68 as its pitch.
+// KIT-ML (21 joints): NV = NF = 64.  The same for either full form: block 0 of the two-block stream holds the same rows.
 __global__ __launch_bounds__(512, 4) void final_joints_x3_kernel(FinalStripArgs p) { final_strip_body<1>(p); }
 
 }  // namespace mld

@@ -573,7 +573,7 @@ int mldhip_text_encode(mldhip_handle* e, const int32_t* ids_host, const int32_t*
 int mldhip_feats2joints(mldhip_handle* e, const float* feats_dev, int32_t B, int32_t T, float* joints_out_dev, void* stream_) {
   if (!e) return MLDHIP_EINVAL;
   DeviceGuard dg(e->device);
-  if (is_actor(e) || e->cfg.nfeats < 67) return e->fail(MLDHIP_ESTATE, "feats2joints implements the HumanML3D layout only (SMPL-based layouts are out of scope)");
+  if (is_actor(e) || e->cfg.nfeats < joint_feat_cols(e)) return e->fail(MLDHIP_ESTATE, "feats2joints implements the HumanML3D / KIT-ML layout (recover_from_ric) only (SMPL-based layouts are out of scope)");
   if (!e->finalized || !e->group_ready[2]) return e->fail(MLDHIP_ESTATE, "feats2joints before finalize / mean,std not loaded");
   if (!feats_dev || !joints_out_dev) return e->fail(MLDHIP_EINVAL, "null pointer");
   if (B < 1 || T < 1 || T > 512) return e->fail(MLDHIP_EINVAL, "B >= 1 and 1 <= T <= 512 required");

@@ -1,4 +1,4 @@
-"""Minimal stand-in for ``HumanML3DDataModule`` (mld/data/HumanML3D.py:11-75): the sampling path only needs
+"""Minimal stand-in for ``HumanML3DDataModule`` / ``KitDataModule`` (mld/data/HumanML3D.py:11-75, mld/data/Kit.py): the sampling path only needs
 ``nfeats``, ``njoints``, the normalisation vectors and ``feats2joints`` -- and the reference's datamodule
 cannot even be constructed without the full dataset, GloVe and pytorch_lightning."""
 from __future__ import annotations
@@ -13,23 +13,44 @@ from . import engine as _engine
 from . import synthetic as syn
 
 
+# name -> (nfeats, njoints, the key of its block under cfg.DATASET); the first two have recover_from_ric joints (12 x njoints - 1 features)
+_LAYOUTS = {"humanml3d": (263, 22, "HUMANML3D"), "kit": (251, 21, "KIT"), "humanact12": (150, 25, "HUMANACT12")}
+
+
+def _from_cfg(cfg, *path):
+    try:
+        for k in path:
+            cfg = cfg[k]
+        return cfg
+    except Exception:
+        return None
+
+
 class HipDataModule:
     name = "humanml3d"
 
     def __init__(self, cfg=None, mean: Optional[np.ndarray] = None, std: Optional[np.ndarray] = None,
-                 nfeats: int = 263, njoints: int = 22, engine_key: Optional[str] = None, name: str = "humanml3d",
+                 nfeats: Optional[int] = None, njoints: Optional[int] = None, engine_key: Optional[str] = None, name: Optional[str] = None,
                  nclasses: int = 12, variant: Optional[str] = None):
-        """name 'humanml3d' (263-d features, 22 joints) or 'humanact12' (rot6d 25x6 = 150-d features, 12 classes;
-        mld/data/HumanAct12.py) -- the latter only carries shapes: its feats2joints needs SMPL."""
+        """name 'humanml3d' (263-d features, 22 joints), 'kit' (KIT-ML: 251-d features, 21 joints; mld/data/Kit.py) or 'humanact12' (rot6d 25x6 =
+        150-d features, 12 classes; mld/data/HumanAct12.py) -- the last only carries shapes: its feats2joints needs SMPL.  What is not passed comes
+        from `cfg`: the name from TEST.DATASETS[0] (how the reference's get_data.py picks the datamodule), the widths from DATASET.NFEATS / NJOINTS
+        (which the reference fills from the datamodule at run time); without a cfg, the layout's own."""
+        if name is None:
+            ds = _from_cfg(cfg, "TEST", "DATASETS")
+            name = str(ds[0]).lower() if ds and str(ds[0]).lower() in _LAYOUTS else "humanml3d"
+        layout = _LAYOUTS.get(name, _LAYOUTS["humanml3d"])
+        if nfeats is None:
+            nfeats = _from_cfg(cfg, "DATASET", "NFEATS") or layout[0]
+        if njoints is None:
+            njoints = _from_cfg(cfg, "DATASET", "NJOINTS") or layout[1]
         self.name, self.nclasses = name, nclasses
         self.variant = variant          # engine registry variant; filled in by MLD when left None
-        self.nfeats, self.njoints = nfeats, njoints
+        self.nfeats, self.njoints = int(nfeats), int(njoints)
+        # mldhip_config fields this datamodule implies (MLD merges them into the model's shared fields): the skeleton feats2joints recovers
+        self._arch = {"nfeats": self.nfeats, "njoints": self.njoints} if name != "humanact12" else {}
         if mean is None or std is None:
-            root = None
-            try:
-                root = cfg.DATASET.HUMANML3D.ROOT
-            except Exception:
-                pass
+            root = _from_cfg(cfg, "DATASET", layout[2], "ROOT")
             if root and os.path.exists(os.path.join(root, "Mean.npy")):      # get_data.py:38-40
                 mean = np.load(os.path.join(root, "Mean.npy"))
                 std = np.load(os.path.join(root, "Std.npy"))
@@ -46,7 +67,7 @@ class HipDataModule:
 
     def _engine(self, device):
         eng = _engine.get_engine(self._engine_key if self._engine_key is not None else device, self.variant or "text",
-                                 want=self._shared_arch)
+                                 want={**self._arch, **self._shared_arch})
         owners = eng.__dict__.setdefault("_owner", {})           # see HipModule.sync_weights: engines are shared per architecture
         if self._loaded_on is not eng or owners.get("mean/std") != id(self):
             eng.load_tensor("mean", self.mean)
@@ -57,8 +78,8 @@ class HipDataModule:
         return eng
 
     def feats2joints(self, features: torch.Tensor, mask=None) -> torch.Tensor:
-        """[B, T, nfeats] -> [B, T, njoints, 3] (HumanML3D.py:41-45 + recover_from_ric), on the tensor's device."""
-        if self.name != "humanml3d":
+        """[B, T, nfeats] -> [B, T, njoints, 3] (HumanML3D.py:41-45 / Kit.py: recover_from_ric with the datamodule's njoints), on the tensor's device."""
+        if self.name not in ("humanml3d", "kit"):
             raise NotImplementedError(f"feats2joints of '{self.name}' maps rot6d features through the SMPL body model "
                                       "(mld/transforms/rots2joints/smplh.py); SMPL is an external asset and out of scope")
         if features.dtype != torch.float32:

@@ -3,7 +3,7 @@
     python -m mld_hip.demo --cfg configs/config_mld_humanml3d.yaml --example demo/example.txt --out_dir results
 
 Reads "<length> <prompt>" lines (mld/utils/demo_utils.py:6-20), samples on the MI355X engine and writes
-``Example_<len>_batch0_<i>.npy`` files of shape (nframe, 22, 3) plus the prompt as .txt.  Offline it
+``Example_<len>_batch0_<i>.npy`` files of shape (nframe, njoints, 3) (22 on HumanML3D, 21 with configs/config_mld_kit.yaml) plus the prompt as .txt.  Offline it
 falls back to synthetic weights / the synthetic text encoder and says so (no checkpoints are reachable)."""
 from __future__ import annotations
 
@@ -29,7 +29,7 @@ def load_example_input(txt_path):
 
 def write_motions(model, texts, lengths, out_dir, replication=1, task="Example", log=print):
     """Sample `replication` times and write the files the reference's demo writes (demo.py:166-194): per motion i
-    ``<task>_<length_i>_batch<id>_<i>.npy`` = joints (nframe, 22, 3) float32 and the prompt under the same name with ``.txt``.
+    ``<task>_<length_i>_batch<id>_<i>.npy`` = joints (nframe, njoints, 3) float32 and the prompt under the same name with ``.txt``.
     The reference never advances ``id`` (demo.py:188), so its replications overwrite each other under ``batch0``; here replication
     r > 0 is kept as ``batch<r>`` and replication 0 carries the reference's exact names.  Returns the list of .npy paths."""
     os.makedirs(out_dir, exist_ok=True)

@@ -87,7 +87,7 @@ def gather_lengths_order(n: int, world: int) -> List[Tuple[int, int]]:
 
 class DataParallelSampler:
     """Shard a list of prompts (or action labels) over the ranks of the default process group; each rank runs the model on its
-    block in chunks of `batch_size` and returns (global_indices, motions) for its block -- joints [len, 22, 3] per prompt for the
+    block in chunks of `batch_size` and returns (global_indices, motions) for its block -- joints [len, njoints, 3] per prompt for the
     text models (``MLD.forward``, mld.py:216-265; also the diffusion-only variant), features [len, nfeats] per label for the
     action model (``MLD.a2m_eval``, mld.py:710-735: its joints need SMPL).
 

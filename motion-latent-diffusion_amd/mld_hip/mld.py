@@ -63,7 +63,8 @@ class MLD(nn.Module):
         # ONE engine for all parts of this model: every part asks the registry for the union of the architecture fields
         # (the fused sample() needs every weight group in one handle); another model with other fields gets its own engine
         shared = {}
-        for m in (self.denoiser, self.vae, self.text_encoder):      # (a HipMldTextEncoder adds the tower's fields: its weights live in the same handle)
+        # (the datamodule first: its skeleton -- njoints, the feature width -- then the networks'; a HipMldTextEncoder adds the tower's fields: its weights live in the same handle)
+        for m in (datamodule, self.denoiser, self.vae, self.text_encoder):
             shared.update(getattr(m, "_arch", {}) or {})
         if hasattr(self.scheduler, "engine_config"):
             shared.update(self.scheduler.engine_config(cfg.model.scheduler.num_inference_timesteps))
@@ -133,7 +134,7 @@ class MLD(nn.Module):
     @torch.no_grad()
     def sample(self, text_emb: torch.Tensor, lengths: List[int], init_latents: Optional[torch.Tensor] = None, seed: Optional[int] = None,
                first_index: int = 0, return_trajectory: bool = False):
-        """text_emb [2B, 1, 768] (uncond half first) -> (joints [B,T,22,3], feats [B,T,nfeats], latents [B,1,D]) on device.
+        """text_emb [2B, 1, 768] (uncond half first) -> (joints [B,T,njoints,3], feats [B,T,nfeats], latents [B,1,D]) on device.
         eta > 0: the step noise of motion m is the engine's Philox stream keyed (seed, first_index + m); `seed` None = drawn from torch's
         generator.  return_trajectory: a fourth result, the latents after every scheduler step [steps, B, D] (mldhip_sample_many_traj; its last
         row is `latents`)."""
@@ -235,7 +236,7 @@ class MLD(nn.Module):
     @torch.no_grad()
     def sample_novae(self, text_emb: torch.Tensor, lengths: List[int], init_latents: Optional[torch.Tensor] = None,
                      step_noise: Optional[torch.Tensor] = None, seed: Optional[int] = None):
-        """Diffusion-only sampling in ONE mldhip_sample_novae call: text_emb [2B, 1, 768] -> (joints [B,T,22,3], feats [B,T,nfeats]).
+        """Diffusion-only sampling in ONE mldhip_sample_novae call: text_emb [2B, 1, 768] -> (joints [B,T,njoints,3], feats [B,T,nfeats]).
         step_noise [steps, B, T, nfeats] injects the scheduler's per-step draws (parity runs); otherwise they come from the
         engine's Philox stream keyed by `seed` (default: drawn from torch's generator, so torch.manual_seed governs it)."""
         lengths = [int(x) for x in lengths]
