@@ -438,6 +438,36 @@ int mldhip_sample_many_traj(mldhip_handle* h, const mldhip_request* reqs, const 
                             float* const* traj_out_dev /* [nreq]; entry i: [num_inference_steps][B_i][latent_size * latent_dim] or NULL */,
                             int32_t nreq, void* stream);
 
+/* Start the reverse loop from a source latent at a chosen step (added at ABI 8 WITHOUT a version bump, as mldhip_sample_many_traj was: one more symbol and one
+ * more struct, nothing existing changed -- callers detect it by its presence).  n = num_inference_steps, t_i = timesteps[i]; every motion of request i starts as
+ * starts[i] says:
+ *   src_latents_dev NULL (first_step 0, noised 0)   x = init_latents * init_noise_sigma,                                     steps 0 .. n-1, as mldhip_sample_many
+ *   src given, 0 <= f < n, noised = 0               x = sqrt(ab_{t_f}) src + sqrt(1 - ab_{t_f}) init_latents,                steps f .. n-1
+ *                                                   (diffusers' add_noise at the first timestep that is run, as its image-to-image pipelines do)
+ *   src given, 0 <= f < n, noised = 1               x = src as it is -- the loop state in front of step f, e.g. row f-1 of a trajectory --
+ *                                                   steps f .. n-1; the request's init_latents_dev is not read and may be NULL
+ * Steps below f are not applied to the motion.  With eta > 0 the Noise contract is unchanged: step i draws with the absolute step index i.  With a trajectory
+ * buffer, rows s < f of the motion are left untouched, rows f .. n-1 are written and row n-1 equals latents_out to the bit.  Decode, feats2joints, the
+ * non-finite counter and the range contract are those of any other call.  Requests of one call may start differently; motions never interact, so a motion's
+ * results do not depend on where its neighbours start.
+ *   starts            [nreq], or NULL.  NULL, or every entry {NULL, 0, 0}: the call IS mldhip_sample_many_traj -- same path, same captured graphs, same bits.
+ *                     A source must be 16-byte aligned ([B_i, latent_size, latent_dim] floats; the kernels read a row four floats at a time).
+ *   keys, traj_out_dev  as for mldhip_sample_many_traj.
+ * Serves text and action engines, eta = 0 and eta > 0, and every loop family (new forms of the loop kernels beside the plain ones, which keep their machine code).
+ * MLDHIP_EINVAL: first_step outside [0, n); first_step != 0 or noised != 0 with a NULL source; noised not 0 or 1; init_latents_dev NULL on a request that is not
+ * resumed; a misaligned source; any non-trivial start on a MLDHIP_VAE_NONE handle.  A call with any source runs as ONE chain over all its motions, also under
+ * "many_pipeline" 1 (sum of B <= max_batch), which is the trajectory rule.  Sources, first steps and the noised flags reach the kernels through an engine-owned
+ * per-motion table uploaded with every call: the captured graph of a shape is replayed with fresh buffers and, on the one-launch loops (persistent and cluster),
+ * with different first steps; the launch-per-GEMM families issue steps min f .. n-1 and keep one graph per (shape, min f).  A workgroup / cluster of a one-launch
+ * loop runs steps min f .. n-1 of ITS motions: a call whose motions all start at f costs about (n - f) / n of a full one. */
+typedef struct mldhip_start {
+  const float* src_latents_dev;   /* [B, latent_size, latent_dim], or NULL = start from noise at step 0 */
+  int32_t first_step;             /* 0 .. num_inference_steps - 1; must be 0 when src_latents_dev is NULL */
+  int32_t noised;                 /* 0: src is a clean latent, mixed with init_latents at t_f; 1: src already is x at step f */
+} mldhip_start;
+int mldhip_sample_many_from(mldhip_handle* h, const mldhip_request* reqs, const mldhip_noise_key* keys /* NULL ok at eta = 0 */,
+                            const mldhip_start* starts /* [nreq] */, float* const* traj_out_dev /* NULL ok */, int32_t nreq, void* stream);
+
 /* Replaces: MldDenoiser.forward(sample, timestep, encoder_hidden_states)[0]
  * (mld/models/architectures/mld_denoiser.py:135-228).  sample [R,1,D], text [R,1,text_dim],
  * out [R,1,D]; any integer timestep in [0, num_train_timesteps). */

@@ -254,6 +254,10 @@ void register_dynamic_lds() {
   (void)hipFuncSetAttribute((const void*)den_loop_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLoopLdsBytes);
   (void)hipFuncSetAttribute((const void*)den_loop_kernel<false, kLoopEta>, hipFuncAttributeMaxDynamicSharedMemorySize, kLoopLdsBytes);
   (void)hipFuncSetAttribute((const void*)den_loop_kernel<true, kLoopEta>, hipFuncAttributeMaxDynamicSharedMemorySize, kLoopLdsBytes);
+  (void)hipFuncSetAttribute((const void*)den_loop_kernel<false, kLoopFrom>, hipFuncAttributeMaxDynamicSharedMemorySize, kLoopLdsBytes);
+  (void)hipFuncSetAttribute((const void*)den_loop_kernel<true, kLoopFrom>, hipFuncAttributeMaxDynamicSharedMemorySize, kLoopLdsBytes);
+  (void)hipFuncSetAttribute((const void*)den_loop_kernel<false, kLoopFromEta>, hipFuncAttributeMaxDynamicSharedMemorySize, kLoopLdsBytes);
+  (void)hipFuncSetAttribute((const void*)den_loop_kernel<true, kLoopFromEta>, hipFuncAttributeMaxDynamicSharedMemorySize, kLoopLdsBytes);
 #if defined(MLDHIP_HOOKS)
   (void)hipFuncSetAttribute((const void*)den_loop_kernel<true, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, kLoopLdsBytes);
 #endif
@@ -265,6 +269,14 @@ void register_dynamic_lds() {
   (void)hipFuncSetAttribute((const void*)den_cluster_eta_kernel<false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, kClLdsBytes);
   (void)hipFuncSetAttribute((const void*)den_cluster_eta_kernel<true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, kClLdsBytes);
   (void)hipFuncSetAttribute((const void*)den_cluster_eta_kernel<false, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, kClLdsBytes);
+  (void)hipFuncSetAttribute((const void*)den_cluster_from_kernel<true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, kClLdsBytes);
+  (void)hipFuncSetAttribute((const void*)den_cluster_from_kernel<false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, kClLdsBytes);
+  (void)hipFuncSetAttribute((const void*)den_cluster_from_kernel<true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, kClLdsBytes);
+  (void)hipFuncSetAttribute((const void*)den_cluster_from_kernel<false, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, kClLdsBytes);
+  (void)hipFuncSetAttribute((const void*)den_cluster_from_eta_kernel<true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, kClLdsBytes);
+  (void)hipFuncSetAttribute((const void*)den_cluster_from_eta_kernel<false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, kClLdsBytes);
+  (void)hipFuncSetAttribute((const void*)den_cluster_from_eta_kernel<true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, kClLdsBytes);
+  (void)hipFuncSetAttribute((const void*)den_cluster_from_eta_kernel<false, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, kClLdsBytes);
 #define MLD_T32_ATTR1(MT, NS, TR, PR) \
   (void)hipFuncSetAttribute((const void*)gemm_tile32_kernel<MT, NS, TR, PR, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, kT32LdsBytes); \
   (void)hipFuncSetAttribute((const void*)gemm_tile32_kernel<MT, NS, TR, PR, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, kT32LdsBytes);
@@ -367,9 +379,11 @@ int create_engine(const mldhip_config& cfg, int device, int num_cus, mldhip_hand
     if (hipMalloc((void**)&x.lens, 2 * Bm * sizeof(int32_t)) != hipSuccess || hipMalloc((void**)&x.lens2, Bm * sizeof(int32_t)) != hipSuccess ||
         hipMalloc((void**)&x.labels, 2 * Bm * sizeof(int32_t)) != hipSuccess || hipMalloc((void**)&x.keys, Bm * sizeof(NoiseKey)) != hipSuccess ||
         hipMemset(x.keys, 0, Bm * sizeof(NoiseKey)) != hipSuccess || hipMalloc((void**)&x.traj, Bm * sizeof(TrajRow)) != hipSuccess ||
-        hipMemset(x.traj, 0, Bm * sizeof(TrajRow)) != hipSuccess) return fail_create("hipMalloc(lens) failed");
+        hipMemset(x.traj, 0, Bm * sizeof(TrajRow)) != hipSuccess || hipMalloc((void**)&x.starts, Bm * sizeof(StartRow)) != hipSuccess ||
+        hipMemset(x.starts, 0, Bm * sizeof(StartRow)) != hipSuccess) return fail_create("hipMalloc(lens) failed");
     x.keys_host.assign(Bm, NoiseKey{0ull, 0ll});
     x.traj_host.assign(Bm, TrajRow{nullptr, 0ll});
+    x.starts_host.assign(Bm, StartRow{nullptr, 0, 0, 0.f, 0.f, {0, 0}});
 #if !defined(MLDHIP_SIM)
     for (hipEvent_t* ev : x.events())
       if (hipEventCreateWithFlags(ev, hipEventDisableTiming) != hipSuccess) return fail_create("event create failed");

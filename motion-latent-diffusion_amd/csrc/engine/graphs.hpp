@@ -75,10 +75,13 @@ int graph_for(E* e, const GraphKey& key, bool text_condition, hipGraphExec_t* ou
       }
       e->sample_part = key.part;
       e->traj_on = key.traj;
+      e->from_on = key.from;
+      e->from_step0 = key.step0;
       const int r = enqueue_sample(e, e->cap_stream, text_condition ? e->text_in : nullptr, e->lat_in, key.B, key.T, nullptr,
                                    key.feats ? e->feats_int : nullptr, key.joints ? e->joints_int : nullptr);
       e->sample_part = 0;
       e->traj_on = false;
+      e->from_on = false;
       return r;
     });
     if (rc) return rc;

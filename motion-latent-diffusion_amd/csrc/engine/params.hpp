@@ -18,7 +18,7 @@ using E = mldhip_engine;
 void bind_context(E* e, int k) {
   WsContext& x = e->ctxs[k];
   for (auto& cv : e->carve) *cv.first = x.ws + cv.second;
-  e->lens_dev = x.lens; e->lens2_dev = x.lens2; e->labels_dev = x.labels; e->keys_dev = x.keys; e->traj_dev = x.traj;
+  e->lens_dev = x.lens; e->lens2_dev = x.lens2; e->labels_dev = x.labels; e->keys_dev = x.keys; e->traj_dev = x.traj; e->starts_dev = x.starts;
   e->cur_ctx = k;
 }
 

@@ -85,12 +85,25 @@ int enqueue_sample(E* e, hipStream_t stream, const float* text, const float* ini
     launch_fused_loop(c, init_lat, B, n, guidance);
   } else {
     const DenView v = den_view(e, 2 * B);
+    // mldhip_sample_many_from: every motion's own start state, then the steps from the call's smallest first step on; the from-form of the final-step kernels
+    // holds the motions that start later
+    const int s_first = e->from_on ? e->from_step0 : 0;
+    if (e->from_on)
+      MLD_COUNTED(c, "init_chain", MLD_LAUNCH(init_chain_from_kernel, dim3(B), dim3(256), 0, c.stream, init_lat, v.lat, v.X0, P(e, "denoiser.query_pos.pe"),
+             (const float*)(e->T1 + (size_t)s_first * D), (const float*)e->TP, B, 1.0f /* init_noise_sigma */, (const StartRow*)e->starts_dev));
+    else
     MLD_COUNTED(c, "init_chain", MLD_LAUNCH(init_chain_kernel, dim3(B), dim3(256), 0, c.stream, init_lat, v.lat, v.X0, P(e, "denoiser.query_pos.pe"), e->T1, e->TP, B, 0, B,
            1.0f /* init_noise_sigma */));
-    for (int s = 0; s < n && !c.rc; ++s) {
+    for (int s = s_first; s < n && !c.rc; ++s) {
       denoiser_body(c, v);
       const float* t1n = (s + 1 < n) ? e->T1 + (size_t)(s + 1) * D : nullptr;
-      if (eta_live(e))
+      if (e->from_on && eta_live(e))
+        MLD_COUNTED(c, "den_final_step", MLD_LAUNCH(den_final_step_eta_from_kernel, dim3(B), dim3(256), 0, c.stream, den_final_args(e, v), v.lat, v.X0, P(e, "denoiser.query_pos.pe"), t1n, B,
+               guidance, ddim_coef(e, e->timesteps[s]), e->keys_dev, s, ddim_eta(e, e->timesteps[s]), traj_table(e), (const StartRow*)e->starts_dev));
+      else if (e->from_on)
+        MLD_COUNTED(c, "den_final_step", MLD_LAUNCH(den_final_step_from_kernel, dim3(B), dim3(256), 0, c.stream, den_final_args(e, v), v.lat, v.X0, P(e, "denoiser.query_pos.pe"), t1n, B,
+               guidance, ddim_coef(e, e->timesteps[s]), traj_table(e), s, (const StartRow*)e->starts_dev));
+      else if (eta_live(e))
         MLD_COUNTED(c, "den_final_step", MLD_LAUNCH(den_final_step_eta_kernel, dim3(B), dim3(256), 0, c.stream, den_final_args(e, v), v.lat, v.X0, P(e, "denoiser.query_pos.pe"), t1n, B,
                guidance, ddim_coef(e, e->timesteps[s]), e->keys_dev, s, ddim_eta(e, e->timesteps[s]), traj_table(e)));
       else

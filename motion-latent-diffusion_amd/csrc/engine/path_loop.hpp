@@ -301,6 +301,15 @@ void launch_fused_loop(Ctx& c, const float* init_lat, int B, int n, float guidan
   a.guidance = guidance; a.init_sigma = 1.0f;
   a.traj = traj_table(e);
   const dim3 grid((B + 7) / 8);
+  if (e->from_on) {                     // mldhip_sample_many_from: the from-forms on the context's start table, with or without noise
+    a.starts = e->starts_dev;
+    if (eta_live(e)) {
+      a.eta = e->loop_eta; a.keys = e->keys_dev;
+      if (x3) MLD_COUNTED(c, "den_loop", MLD_LAUNCH((den_loop_kernel<true, kLoopFromEta>), grid, dim3(512), kLoopLdsBytes, c.stream, a));
+      else MLD_COUNTED(c, "den_loop", MLD_LAUNCH((den_loop_kernel<false, kLoopFromEta>), grid, dim3(512), kLoopLdsBytes, c.stream, a));
+    } else if (x3) MLD_COUNTED(c, "den_loop", MLD_LAUNCH((den_loop_kernel<true, kLoopFrom>), grid, dim3(512), kLoopLdsBytes, c.stream, a));
+    else MLD_COUNTED(c, "den_loop", MLD_LAUNCH((den_loop_kernel<false, kLoopFrom>), grid, dim3(512), kLoopLdsBytes, c.stream, a));
+  } else
   if (eta_live(e)) {                    // stochastic DDIM: the step's second table row + the call's noise keys
     a.eta = e->loop_eta; a.keys = e->keys_dev;
     if (x3) MLD_COUNTED(c, "den_loop", MLD_LAUNCH((den_loop_kernel<true, kLoopEta>), grid, dim3(512), kLoopLdsBytes, c.stream, a));
@@ -351,7 +360,10 @@ void launch_cluster_chunk(Ctx& c, const float* init_lat, int B, int s_base, int 
   const K plain[2][2] = {{den_cluster_kernel<false, 4>, den_cluster_kernel<false, 8>}, {den_cluster_kernel<true, 4>, den_cluster_kernel<true, 8>}};
   const K eta[2][2] = {{den_cluster_eta_kernel<false, 4>, den_cluster_eta_kernel<false, 8>}, {den_cluster_eta_kernel<true, 4>, den_cluster_eta_kernel<true, 8>}};
   if (eta_live(e)) { a.eta = e->loop_eta; a.keys = e->keys_dev; }      // stochastic DDIM: the step's second table row + the call's noise keys
-  const K k = (eta_live(e) ? eta : plain)[e->cluster_wt ? 1 : 0][cg == 8 ? 1 : 0];
+  const K from[2][2] = {{den_cluster_from_kernel<false, 4>, den_cluster_from_kernel<false, 8>}, {den_cluster_from_kernel<true, 4>, den_cluster_from_kernel<true, 8>}};
+  const K from_eta[2][2] = {{den_cluster_from_eta_kernel<false, 4>, den_cluster_from_eta_kernel<false, 8>}, {den_cluster_from_eta_kernel<true, 4>, den_cluster_from_eta_kernel<true, 8>}};
+  if (e->from_on) a.starts = e->starts_dev;                            // mldhip_sample_many_from: the from-forms on the context's start table
+  const K k = (e->from_on ? (eta_live(e) ? from_eta : from) : (eta_live(e) ? eta : plain))[e->cluster_wt ? 1 : 0][cg == 8 ? 1 : 0];
   MLD_COUNTED(c, "den_cluster", MLD_LAUNCH_CORESIDENT(k, grid, dim3(512), kClLdsBytes, c.stream, a));
 }
 

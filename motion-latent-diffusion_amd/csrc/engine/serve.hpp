@@ -148,6 +148,25 @@ int upload_traj(E* e, const mldhip_request* rq, float* const* traj, int nreq, hi
   return MLDHIP_OK;
 }
 
+// The start table of a coalesced call into the bound context's array (mldhip_sample_many_from): motion k of request i gets {src_i + k * D, first_step_i, noised_i}
+// and the two add_noise coefficients of its first step -- or the all-zero entry (start from noise at step 0) when the request has no source.  Host copy + upload
+// with every call, like the trajectory table: the kernels never see a caller pointer or a first step as a launch argument.  Returns the call's smallest first step.
+int upload_starts(E* e, const mldhip_request* rq, const mldhip_start* starts, int nreq, hipStream_t stream, int* step0) {
+  WsContext& x = e->ctxs[e->cur_ctx];
+  const long long D = (long long)e->cfg.latent_size * e->cfg.latent_dim;
+  int o = 0, lo = e->cfg.num_inference_steps - 1;
+  for (int i = 0; i < nreq; ++i) {
+    const mldhip_start& s = starts[i];
+    const DdimCoef k = ddim_coef(e, e->timesteps[s.first_step]);
+    lo = std::min(lo, (int)s.first_step);
+    for (int m = 0; m < rq[i].B; ++m, ++o)
+      x.starts_host[o] = s.src_latents_dev ? StartRow{s.src_latents_dev + m * D, s.first_step, s.noised, k.sqrt_at, k.sqrt_1mat, {0, 0}} : StartRow{nullptr, 0, 0, 0.f, 0.f, {0, 0}};
+  }
+  HIP_TRY(e, hipMemcpyAsync(e->starts_dev, x.starts_host.data(), (size_t)o * sizeof(StartRow), hipMemcpyHostToDevice, stream));
+  *step0 = lo;
+  return MLDHIP_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- mldhip_sample_many, pipelined
 // "many_pipeline": the requests of a mldhip_sample_many call ONE AFTER THE OTHER, each on the single-request path (the reverse loop of a request is one cluster
 // launch, kernels/loop_cluster.hpp) -- the reference's own shape, batch after batch (mld.py:618-672, test.py:116-119) -- with the two halves of consecutive requests
@@ -385,7 +404,8 @@ int sample_many_pipelined(E* e, const mldhip_request* rq, int nreq, const std::v
 // the engine's staging buffers (unconditional halves first, as one big CFG batch), outputs scattered per request with
 // each request's own Tmax as its row pitch.  Motions never interact (attention is per sample), so results equal the
 // per-request calls up to the summation order of the kernel family picked for the larger row count.
-int gather_requests(Ctx& c, const mldhip_request* rq, int nreq, int Btot) {
+// lat_of (or nullptr: the requests' init_latents_dev): the [B_i][D] buffer gathered as request i's start latents
+int gather_requests(Ctx& c, const mldhip_request* rq, int nreq, int Btot, const float* const* lat_of = nullptr) {
   E* e = c.e;
   const bool action = is_action(e);
   const long long D = e->cfg.latent_dim, TD = e->cfg.text_dim;
@@ -393,7 +413,7 @@ int gather_requests(Ctx& c, const mldhip_request* rq, int nreq, int Btot) {
   int o = 0, bmax = 0;
   for (int i = 0; i < kMaxRequests; ++i) { ga.text[i] = nullptr; ga.lat[i] = nullptr; ga.off[i] = 0; ga.nb[i] = 0; }
   for (int i = 0; i < nreq; ++i) {
-    ga.text[i] = action ? nullptr : rq[i].text_emb_dev; ga.lat[i] = rq[i].init_latents_dev; ga.off[i] = o; ga.nb[i] = rq[i].B;
+    ga.text[i] = action ? nullptr : rq[i].text_emb_dev; ga.lat[i] = lat_of ? lat_of[i] : rq[i].init_latents_dev; ga.off[i] = o; ga.nb[i] = rq[i].B;
     o += rq[i].B; bmax = std::max(bmax, (int)rq[i].B);
   }
   ga.text_in = e->text_in; ga.lat_in = e->lat_in; ga.Btot = Btot; ga.TD = (int)TD; ga.D = (int)D;
@@ -420,8 +440,10 @@ int scatter_results(Ctx& c, const mldhip_request* rq, int nreq, const std::vecto
 }
 
 // `traj` (or nullptr): per request, the [steps][B_i][D] buffer that receives the latents after every scheduler step (mldhip_sample_many_traj); a call that asks
-// for any runs as one chain, also under "many_pipeline" 1
-int sample_many_impl(E* e, const mldhip_request* rq, int nreq, hipStream_t stream, const mldhip_noise_key* keys = nullptr, float* const* traj = nullptr) {
+// for any runs as one chain, also under "many_pipeline" 1.  `starts` (or nullptr): per request, where its motions enter the loop (mldhip_sample_many_from; checked by
+// the caller); a call with any source is one chain as well, on the from-forms of the loop kernels
+int sample_many_impl(E* e, const mldhip_request* rq, int nreq, hipStream_t stream, const mldhip_noise_key* keys = nullptr, float* const* traj = nullptr,
+                     const mldhip_start* starts = nullptr) {
   if (!e->finalized) return e->fail(MLDHIP_ESTATE, "mldhip_sample_many before mldhip_finalize_weights");
   heal_cluster(e);
   const bool action = is_action(e);
@@ -430,7 +452,8 @@ int sample_many_impl(E* e, const mldhip_request* rq, int nreq, hipStream_t strea
   std::vector<int32_t> lens, tmax(nreq, 0);
   for (int i = 0; i < nreq; ++i) {
     const mldhip_request& r = rq[i];
-    if (!r.init_latents_dev || (action ? !r.actions_host : !r.text_emb_dev)) return e->fail(MLDHIP_EINVAL, "request %d: null input pointer", i);
+    const bool resumes = starts && starts[i].src_latents_dev && starts[i].noised;      // the loop state is the source as it is: init_latents is not read
+    if ((!r.init_latents_dev && !resumes) || (action ? !r.actions_host : !r.text_emb_dev)) return e->fail(MLDHIP_EINVAL, "request %d: null input pointer", i);
     if (r.joints_out_dev && is_actor(e)) return e->fail(MLDHIP_ESTATE, "joints of the ActorVae feature layout need SMPL (out of scope)");
     if (int rc = validate_lengths(e, r.lengths_host, r.B, &tmax[i])) return rc;
     if (action)
@@ -445,7 +468,9 @@ int sample_many_impl(E* e, const mldhip_request* rq, int nreq, hipStream_t strea
     return e->fail(MLDHIP_ESTATE, "mldhip_sample_many needs denoiser.*, vae.decoder.* (and mean/std for joints) loaded");
   bool want_t = false;
   for (int i = 0; traj && i < nreq; ++i) want_t = want_t || traj[i];
-  if (e->many_pipeline && nreq >= 2 && e->ctxs.size() >= 2 && !want_t) {
+  bool want_s = false;
+  for (int i = 0; starts && i < nreq; ++i) want_s = want_s || starts[i].src_latents_dev;
+  if (e->many_pipeline && nreq >= 2 && e->ctxs.size() >= 2 && !want_t && !want_s) {
     bool ok = true;
     for (int i = 0; i < nreq; ++i) ok = ok && use_cluster(e, rq[i].B) && (rq[i].feats_out_dev || rq[i].joints_out_dev);
     if (ok) return sample_many_pipelined(e, rq, nreq, tmax, stream, keys);
@@ -457,6 +482,8 @@ int sample_many_impl(E* e, const mldhip_request* rq, int nreq, hipStream_t strea
   HIP_TRY(e, hipMemcpyAsync(e->lens_dev, lens.data(), (size_t)Btot * sizeof(int32_t), hipMemcpyHostToDevice, stream));
   if (keys) if (int rc = upload_keys(e, rq, keys, 0, nreq, stream)) return rc;
   if (want_t) if (int rc = upload_traj(e, rq, traj, nreq, stream)) return rc;
+  int step0 = 0;
+  if (want_s) if (int rc = upload_starts(e, rq, starts, nreq, stream, &step0)) return rc;
   if (action) {
     // stage_actions' layout for the gathered batch, built on the host (the requests' labels are not contiguous): one copy
     std::vector<int32_t> lab(2 * (size_t)Btot, 0);
@@ -465,21 +492,31 @@ int sample_many_impl(E* e, const mldhip_request* rq, int nreq, hipStream_t strea
     HIP_TRY(e, hipMemcpyAsync(e->labels_dev, lab.data(), lab.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
   }
   Ctx cio{e, stream};
-  if (int rc = gather_requests(cio, rq, nreq, Btot)) return rc;
+  std::vector<const float*> lat_of;
+  if (want_s) {      // a resumed request may come without init_latents: its source stands in for the gather (same shape; the from-forms never read those rows)
+    for (int i = 0; i < nreq; ++i) lat_of.push_back(rq[i].init_latents_dev ? rq[i].init_latents_dev : starts[i].src_latents_dev);
+  }
+  if (int rc = gather_requests(cio, rq, nreq, Btot, want_s ? lat_of.data() : nullptr)) return rc;
   const float* text = action ? nullptr : e->text_in;
 #if !defined(MLDHIP_SIM)
   if (replays(e, Btot)) {
     hipGraphExec_t exec = nullptr;
     GraphKey key{Btot, T, want_f, want_j};
     key.traj = want_t;
+    key.from = want_s;
+    // the one-launch loops read the first steps from the table (one graph for all of them); the other families' host loop issues steps step0 .. n-1
+    key.step0 = want_s && !(use_cluster(e, Btot) || use_fused(e, Btot)) ? step0 : 0;
     if (int rc = graph_for(e, key, text != nullptr, &exec)) return rc;
     HIP_TRY(e, hipGraphLaunch(exec, stream));
   } else
 #endif
   {
     e->traj_on = want_t;
+    e->from_on = want_s;
+    e->from_step0 = step0;
     const int rc = enqueue_sample(e, stream, text, e->lat_in, Btot, T, nullptr, want_f ? e->feats_int : nullptr, want_j ? e->joints_int : nullptr);
     e->traj_on = false;
+    e->from_on = false;
     if (rc) return rc;
   }
   return scatter_results(cio, rq, nreq, tmax, T);

@@ -34,7 +34,9 @@ struct GraphKey {
   bool dec_only = false;   // the decode half of a call alone (reads the context's latents): the pipelined form of mldhip_sample_many ("many_pipeline")
   int part = 0;            // loop-only graphs of the pipelined form: 1 = what precedes the cluster launch (condition rows, flag clear), 2 = the cluster launch + its non-finite count; 0 = everything
   bool traj = false;       // the reverse loop stores every step's latents through the context's trajectory table (mldhip_sample_many_traj); calls without one pass a NULL table and keep their graphs
-  bool operator<(const GraphKey& o) const { return std::tie(B, T, feats, joints, dec_only, part, traj) < std::tie(o.B, o.T, o.feats, o.joints, o.dec_only, o.part, o.traj); }
+  bool from = false;       // the reverse loop takes every motion's start from the context's start table (mldhip_sample_many_from): the from-forms of the loop kernels
+  int step0 = 0;           // ... on the launch-per-GEMM families, the first step the host loop issues (the launch count depends on it); 0 on the one-launch loops, whose kernels read it from the table: one graph for any first steps
+  bool operator<(const GraphKey& o) const { return std::tie(B, T, feats, joints, dec_only, part, traj, from, step0) < std::tie(o.B, o.T, o.feats, o.joints, o.dec_only, o.part, o.traj, o.from, o.step0); }
 };
 
 }  // namespace
@@ -50,6 +52,8 @@ struct WsContext {
   std::vector<NoiseKey> keys_host;     // stable host copy of what is uploaded to `keys`
   TrajRow* traj = nullptr;             // [max_batch] trajectory entry per motion of the call (mldhip_sample_many_traj; uploaded with every such call, like keys: a replay writes to fresh caller buffers)
   std::vector<TrajRow> traj_host;      // stable host copy of what is uploaded to `traj`
+  StartRow* starts = nullptr;          // [max_batch] start entry per motion of the call (mldhip_sample_many_from; uploaded with every such call, like traj: a replay reads fresh caller buffers and first steps)
+  std::vector<StartRow> starts_host;   // stable host copy of what is uploaded to `starts`
   std::vector<int32_t> clip_tab_host;  // text tower: stable host copy of the call's row / prompt tables (engine/path_clip.hpp)
   bool used = false;
   unsigned long long seed_host = 0;   // stable host copy of the Philox seed while it is uploaded to seed_slot
@@ -63,7 +67,7 @@ struct WsContext {
   std::vector<hipEvent_t*> events() { return {&done, &loop_done, &pre_done}; }   // created with the context, destroyed with it (engine/create.hpp)
 #endif
   // every device allocation the context owns: teardown frees what is listed HERE (a new buffer is added beside its declaration, nowhere else)
-  std::vector<void**> device_buffers() { return {(void**)&ws, (void**)&lens, (void**)&lens2, (void**)&labels, (void**)&keys, (void**)&traj}; }
+  std::vector<void**> device_buffers() { return {(void**)&ws, (void**)&lens, (void**)&lens2, (void**)&labels, (void**)&keys, (void**)&traj, (void**)&starts}; }
 };
 
 struct mldhip_engine {
@@ -129,6 +133,9 @@ struct mldhip_engine {
   NoiseKey* keys_dev = nullptr;   // the bound context's noise keys
   TrajRow* traj_dev = nullptr;    // the bound context's trajectory table
   bool traj_on = false;           // set while a call that asked for a trajectory is issued / captured: the reverse loop gets the table (else NULL: no store)
+  StartRow* starts_dev = nullptr; // the bound context's start table
+  bool from_on = false;           // set while a call with a source start is issued / captured: the reverse loop runs its from-form on the table
+  int from_step0 = 0;             // ... the smallest first step of the call (the launch-per-GEMM families' host loop starts there)
   bool noise_off = false;         // set while the range probe runs: it measures arithmetic on the eta = 0 kernels, also on an eta > 0 handle
   // denoiser
   float *X0, *Ha, *Hb, *H1, *S[8], *QKV, *AO, *FF, *lat, *T1, *temb0, *tmid, *text_bias, *t1_one, *temb0_one, *time_b2pe;

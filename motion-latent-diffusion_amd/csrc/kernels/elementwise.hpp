@@ -65,6 +65,36 @@ struct NoiseKey { unsigned long long seed; long long index; };
 // Trajectory entry of one motion of a call (mldhip_sample_many_traj): the motion's row in step 0 of its request's [steps][B_i][256] buffer (NULL: no
 // trajectory for this motion) and the floats between consecutive steps (B_i x 256).  The reverse loop stores prev_sample of step s to row0 + s * step_stride.
 struct TrajRow { float* row0; long long step_stride; };
+// Start entry of one motion of a call (mldhip_sample_many_from): src == NULL: the motion starts from init_latents * init_noise_sigma at step 0 (first_step is 0);
+// otherwise the loop state in front of step first_step is c_src * src + c_noise * init_latents (noised == 0: diffusers' add_noise at timesteps[first_step]; the
+// two coefficients are the step's sqrt(ab_t), sqrt(1 - ab_t), the first two words of its DdimCoef) or src as it is (noised == 1), and steps below first_step leave
+// the motion alone.  src points at the motion's own row of the caller's buffer.
+struct StartRow { const float* src; int first_step; int noised; float c_src, c_noise; int pad[2]; };
+static_assert(sizeof(StartRow) == 32, "StartRow is uploaded as an array");
+
+// init_chain_kernel for a call that starts from sources (mldhip_sample_many_from): the same token rows with each motion's own start state (StartRow) and the time row of the
+// call's first executed step (t1_row = T1 + step0 * 256); the whole call is one chain (b0 = 0, Bc = B).  grid = B, block = 256.
+__global__ __launch_bounds__(256) void init_chain_from_kernel(const float* __restrict__ init_lat, float* __restrict__ lat,
+                                                              float* __restrict__ X0, const float* __restrict__ pe0,
+                                                              const float* __restrict__ t1_row, const float* __restrict__ TP,
+                                                              int B, float init_sigma, const StartRow* __restrict__ starts) {
+  const int b = blockIdx.x, d = threadIdx.x, R = 2 * B;
+  const StartRow st = starts[b];                         // (block-uniform)
+  float x;
+  if (!st.src) x = init_lat[(long long)b * 256 + d] * init_sigma;
+  else if (st.noised) x = ld1_global(st.src + d);
+  else x = st.c_src * ld1_global(st.src + d) + st.c_noise * init_lat[(long long)b * 256 + d];
+  lat[(long long)b * 256 + d] = x;
+  const float tok = x + pe0[d];
+  X0[(long long)b * 256 + d] = tok;
+  X0[(long long)(B + b) * 256 + d] = tok;
+  const float tt = t1_row[d];
+  X0[(long long)(R + b) * 256 + d] = tt;
+  X0[(long long)(R + B + b) * 256 + d] = tt;
+  X0[(long long)(2 * R + b) * 256 + d] = TP[(long long)b * 256 + d];
+  X0[(long long)(2 * R + B + b) * 256 + d] = TP[(long long)(B + b) * 256 + d];
+}
+
 
 // LayerNorm over rows of width 256: one wave per row, 4 rows per workgroup.
 __global__ __launch_bounds__(256) void layernorm_rows_kernel(const float* __restrict__ X, float* __restrict__ Y,

@@ -95,6 +95,7 @@ struct ClusterArgs {
   const float* eta = nullptr;        // den_cluster_eta_kernel: [n][2] DdimEta per step
   const NoiseKey* keys = nullptr;    // ... [B] noise key per motion of the call
   const TrajRow* traj = nullptr;     // mldhip_sample_many_traj: [B] trajectory entry per motion of the call, or NULL; member 0 stores, as with `lat`
+  const StartRow* starts = nullptr;  // den_cluster_from_kernel / den_cluster_from_eta_kernel: [B] start entry per motion of the call
 };
 
 #if defined(MLDHIP_SIM)
@@ -135,7 +136,7 @@ __global__ void poke_cluster_flag_kernel(unsigned* __restrict__ word, unsigned v
 // skip linear = 32 output columns per member with K on four wave pairs).
 template <bool WT, int CG>
 __global__ __launch_bounds__(512, 2) void den_cluster_kernel(ClusterArgs p) {
-  constexpr bool ETA = false;
+  constexpr bool ETA = false, FROM = false;
 #include "loop_cluster_body.hpp"
 }
 
@@ -144,7 +145,20 @@ __global__ __launch_bounds__(512, 2) void den_cluster_kernel(ClusterArgs p) {
 // what it was (an always-inlined body schedules it differently).
 template <bool WT, int CG>
 __global__ __launch_bounds__(512, 2) void den_cluster_eta_kernel(ClusterArgs p) {
-  constexpr bool ETA = true;
+  constexpr bool ETA = true, FROM = false;
+#include "loop_cluster_body.hpp"
+}
+
+// The from-forms (mldhip_sample_many_from): per-motion start states and first steps from p.starts, flag epochs counted from the cluster's own first step
+// (loop_cluster_body.hpp FROM).  Kernels of their own next to the two above, which keep their machine code.
+template <bool WT, int CG>
+__global__ __launch_bounds__(512, 2) void den_cluster_from_kernel(ClusterArgs p) {
+  constexpr bool ETA = false, FROM = true;
+#include "loop_cluster_body.hpp"
+}
+template <bool WT, int CG>
+__global__ __launch_bounds__(512, 2) void den_cluster_from_eta_kernel(ClusterArgs p) {
+  constexpr bool ETA = true, FROM = true;
 #include "loop_cluster_body.hpp"
 }
 

@@ -1,5 +1,8 @@
 // Body of den_cluster_kernel / den_cluster_eta_kernel (loop_cluster.hpp), included inside both: in scope are the kernel argument `p` (ClusterArgs) and
-// the compile-time constants WT, CG and ETA.  No include guard on purpose.
+// the compile-time constants WT, CG, ETA and FROM.  No include guard on purpose.
+// FROM (den_cluster_from_kernel / den_cluster_from_eta_kernel, mldhip_sample_many_from): every motion's start state comes from its StartRow, the cluster's step loop
+// begins at step0 = the smallest first step of its real motions (all members read the same eight entries, so they agree), and the flag epochs count from step0 --
+// a from-launch holds the epochs a plain launch of n - step0 steps holds, so the entry check, the `mute` injection and the parity of the exchange buffers are unchanged.
   constexpr int kM = 3 * CG;
 #if defined(MLDHIP_SIM)
   float* smem = reinterpret_cast<float*>(hipsim::blk().dyn_smem.data());
@@ -286,7 +289,28 @@
   };
 
   // ---- prologue: latents, parameters of layer 0, the first step's rows, the ring; placement census when plain stores were asked for
-  {
+  int step0 = 0;                                 // FROM: the first step this cluster runs
+  [[maybe_unused]] int myf = 0;                  // FROM: first step of this wave's motion (s0 + wave; a ragged cluster's missing motions repeat the last real one)
+  if constexpr (FROM) {
+    const int c = tid >> 6, c4 = tid & 63;
+    int s = s0 + c;
+    s = s < p.s_end ? s : p.s_end - 1;
+    const StartRow st = p.starts[s];             // (wave-uniform)
+    F4 v = F4{0.f, 0.f, 0.f, 0.f};
+    if (!(st.src && st.noised)) v = ld4(p.init_lat + (long long)s * 256 + c4 * 4);
+    if (!st.src) {
+      v = F4{v.x * p.init_sigma, v.y * p.init_sigma, v.z * p.init_sigma, v.w * p.init_sigma};
+    } else {
+      const F4 u = ld4_global(st.src + c4 * 4);
+      const float ca = p.ddim[st.first_step * 4], cn = p.ddim[st.first_step * 4 + 1];      // add_noise at the first timestep that is run
+      v = st.noised ? u : F4{ca * u.x + cn * v.x, ca * u.y + cn * v.y, ca * u.z + cn * v.z, ca * u.w + cn * v.w};
+    }
+    st4(lats + c * 256 + c4 * 4, v);
+    myf = st.first_step;
+    step0 = p.n - 1;
+    for (int k = 0; k < 8; ++k)
+      if (s0 + k < p.s_end) { const int fk = p.starts[s0 + k].first_step; step0 = fk < step0 ? fk : step0; }
+  } else {
     const int c = tid >> 6, c4 = tid & 63;
     int s = s0 + c;
     s = s < p.s_end ? s : p.s_end - 1;
@@ -297,7 +321,7 @@
   prm_store(0);
   if constexpr (CG == 4) { if (tid == 0) ctl[2] = 0u; }      // (wait_one of the 12-workgroup form)
   __syncthreads();
-  assemble(0);
+  assemble(step0);
 #pragma unroll
   for (int j = 0; j < kClRing; ++j) gload(j);
   bool wt = true;
@@ -331,11 +355,11 @@
               f16_bits_value(h.y) + f16_bits_value(lo.y), f16_bits_value(h.y >> 16) + f16_bits_value(lo.y >> 16)};
   };
 
-  for (int step = 0; step < p.n; ++step) {
+  for (int step = step0; step < p.n; ++step) {
     goff = wbase + (unsigned)(kClRing * kClFragFloats);
     for (int l = 0; l < p.L; ++l) {
       const float* sm = prm + pbuf * kLfPrmFloats;
-      const unsigned epoch = (unsigned)(step * p.L + l) + 1u;
+      const unsigned epoch = (unsigned)((step - step0) * p.L + l) + 1u;
       const unsigned par = epoch & 1u;
       const unsigned own_mask = ((1u << CG) - 1u) << (CG * tk), ao_mask = 0xFu << (CG * tk);
       fresh();
@@ -654,7 +678,7 @@
         __syncthreads();
         fresh();
         f32x4 z0 = zero4, z1 = zero4;
-        const unsigned zepoch = 16u + (unsigned)(step * nb + si) + 1u, zpar = zepoch & 1u;
+        const unsigned zepoch = 16u + (unsigned)((step - step0) * nb + si) + 1u, zpar = zepoch & 1u;
         if constexpr (CG == 4) {
         const float* abuf = wave < 4 ? Xs + 16 * tk * kClXs : As;
         F4 x[2][2];
@@ -736,9 +760,15 @@
           nv[i] = sap * x0 + s1map * eps;
         }
         }
+        bool hold = false;
+        if constexpr (FROM) {                      // a motion that has not started yet keeps its latent: a select on the stored value (wave-uniform)
+          hold = step < myf;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) nv[i] = hold ? xtv[i] : nv[i];
+        }
         st4(lp, F4{nv[0], nv[1], nv[2], nv[3]});
         // the step's prev_sample to the motion's trajectory row: member 0 (as with p.lat), wave w = motion s0 + w (wave-uniform test; no barrier, no LDS)
-        if (member == 0 && p.traj && s0 + wave < p.s_end) {
+        if (member == 0 && p.traj && s0 + wave < p.s_end && !hold) {
           const TrajRow tr = p.traj[s0 + wave];
           if (tr.row0) st4_global(tr.row0 + (long long)step * tr.step_stride + lane * 4, F4{nv[0], nv[1], nv[2], nv[3]});
         }

@@ -75,11 +75,16 @@ struct LoopArgs {
   const float* eta = nullptr;            // den_loop_kernel<X3, kLoopEta>: [n][2] DdimEta per step
   const NoiseKey* keys = nullptr;        // ... [B] noise key per motion of the call
   const TrajRow* traj = nullptr;         // mldhip_sample_many_traj: [B] trajectory entry per motion of the call, or NULL (no trajectory: nothing is stored)
+  const StartRow* starts = nullptr;      // den_loop_kernel<X3, kLoopFrom / kLoopFromEta>: [B] start entry per motion of the call
 };
 
 // den_loop_kernel<X3, kLoopEta>: the stochastic-DDIM form (eta > 0, include/mldhip.h "Noise contract") of the production loop.  It takes a value of
 // the variant parameter rather than a template parameter of its own, so the eta = 0 instantiations keep their names and their machine code.
 constexpr int kLoopEta = 6;
+// den_loop_kernel<X3, kLoopFrom> / <X3, kLoopFromEta>: the from-forms (mldhip_sample_many_from) of the production loop and of its eta form, further values of the
+// same parameter for the same reason.  The prologue builds every motion's start state from its StartRow, the workgroup's step loop begins at the smallest first
+// step of its real motions, and a motion whose own first step lies behind the current one keeps its latent at the end of the step.
+constexpr int kLoopFrom = 7, kLoopFromEta = 8;
 
 #ifndef LF_EXP
 #define LF_EXP 0          // tools/loopbench experiments (measurement builds with WRONG results; 0 in the library): 1 / 4 = linear1 / linear2 re-use stale A
@@ -141,7 +146,8 @@ __global__ __launch_bounds__(512) void pack_loop_stream_kernel(const float* __re
 // 2 r + (g ^ (r >> 2)) mod 16 is still a permutation inside each of the instruction's four lane groups; tests/test_lds_layout.py).
 template <bool X3, int DBG = 0>
 __global__ __launch_bounds__(512, 2) void den_loop_kernel(LoopArgs p) {
-  constexpr bool ETA = DBG == kLoopEta;   // stochastic DDIM: the step's second table row, sigma z added at the DDIM update (z drawn per (r < 8, cb) quad)
+  constexpr bool FROM = DBG == kLoopFrom || DBG == kLoopFromEta;   // mldhip_sample_many_from: per-motion start states and first steps (p.starts)
+  constexpr bool ETA = DBG == kLoopEta || DBG == kLoopFromEta;   // stochastic DDIM: the step's second table row, sigma z added at the DDIM update (z drawn per (r < 8, cb) quad)
   constexpr int kLoopRing = LF_RING;      // items in flight per lane.  (r03: 8 spilled ring slots around the epilogues at the 256-register cap and lost, 33.1 vs
                                           // 29.3 ms; with the skip linears pinned -- pin_acc: 194 registers, no scratch -- 8 wins: 19.07 / 18.65 ms at 1 280 motions for
                                           // no pins + ring 4 / pins + ring 8, 25.25 / 24.99 ms at 2 048, profiles/r04_loop_experiments.json)
@@ -453,7 +459,31 @@ __global__ __launch_bounds__(512, 2) void den_loop_kernel(LoopArgs p) {
   };
 
   // ---- prologue: latents; first step's token rows; the first kLoopRing items into the ring
-  {
+  int step0 = 0;                                   // FROM: the first step this workgroup runs = the smallest first step of its real motions
+  [[maybe_unused]] int myf = 0;                    // FROM: first step of this lane's motion (row r & 7; rows beyond B repeat motion B - 1, as everywhere)
+  if constexpr (FROM) {
+    const int c = tid >> 6, c4 = tid & 63;
+    int s = s0 + c;
+    s = s < p.B ? s : p.B - 1;
+    const StartRow st = p.starts[s];               // (wave-uniform: a wave per motion here)
+    F4 v = F4{0.f, 0.f, 0.f, 0.f};
+    if (!(st.src && st.noised)) v = ld4(p.init_lat + (long long)s * 256 + c4 * 4);
+    if (!st.src) {
+      v = F4{v.x * p.init_sigma, v.y * p.init_sigma, v.z * p.init_sigma, v.w * p.init_sigma};
+    } else {
+      const F4 u = ld4_global(st.src + c4 * 4);
+      // add_noise at the first timestep that is run (diffusers' image-to-image pipelines): sqrt(ab_t) src + sqrt(1 - ab_t) noise
+      const float ca = p.ddim[st.first_step * 4], cn = p.ddim[st.first_step * 4 + 1];
+      v = st.noised ? u : F4{ca * u.x + cn * v.x, ca * u.y + cn * v.y, ca * u.z + cn * v.z, ca * u.w + cn * v.w};
+    }
+    st4(lats + c * 256 + c4 * 4, v);
+    step0 = p.n - 1;
+    for (int k = 0; k < 8; ++k)
+      if (s0 + k < p.B) { const int fk = p.starts[s0 + k].first_step; step0 = fk < step0 ? fk : step0; }
+    int sm_ = s0 + (r & 7);
+    sm_ = sm_ < p.B ? sm_ : p.B - 1;
+    myf = p.starts[sm_].first_step;
+  } else {
     const int c = tid >> 6, c4 = tid & 63;
     int s = s0 + c;
     s = s < p.B ? s : p.B - 1;
@@ -485,7 +515,7 @@ __global__ __launch_bounds__(512, 2) void den_loop_kernel(LoopArgs p) {
   prm_fetch(0);
   prm_store(0);
   __syncthreads();
-  assemble(0);
+  assemble(step0);
   __syncthreads();
 #pragma unroll
   for (int j = 0; j < kLoopRing; ++j) gload(j);
@@ -496,7 +526,7 @@ __global__ __launch_bounds__(512, 2) void den_loop_kernel(LoopArgs p) {
   const float* aa = As + r * kLfXs + gs4;          // ... of the attention output / the hidden-activation blocks
 
   if constexpr (DBG == 5) tph = clock_pinned();
-  for (int step = 0; step < p.n; ++step) {
+  for (int step = step0; step < p.n; ++step) {
     goff = (unsigned)tid * 8u + (unsigned)(kLoopRing * kLoopItemFloats);
     for (int l = 0; l < p.L; ++l) {
       float x[2][3][4];                            // norm2 output of this layer at this lane's positions (dies inside the layer: the next one reads Xs)
@@ -788,11 +818,17 @@ __global__ __launch_bounds__(512, 2) void den_loop_kernel(LoopArgs p) {
               nv[i] = sap * x0 + s1map * eps;
             }
             }
+            bool hold = false;
+            if constexpr (FROM) {                    // a motion that has not started yet keeps its latent: a select on the stored value
+              hold = step < myf;
+#pragma unroll
+              for (int i = 0; i < 4; ++i) nv[i] = hold ? xtv[i] : nv[i];
+            }
             st4(lp, F4{nv[0], nv[1], nv[2], nv[3]});
             // the step's prev_sample to the motion's trajectory row (no barrier, no LDS: the values are in registers; real motions only).  p.traj is
             // wave-uniform; the motion test is per lane here (r = lane & 15: a wave holds the 8 motions of the workgroup, unlike the cluster loop's one
             // motion per wave), so the 16-byte table entry is a per-lane load of 8 distinct addresses, and the lanes of missing motions are masked off
-            if (p.traj && s0 + r < p.B) {
+            if (p.traj && s0 + r < p.B && !hold) {
               const TrajRow tr = p.traj[s0 + r];
               if (tr.row0) st4_global(tr.row0 + (long long)step * tr.step_stride + (cb * 128 + cq0), F4{nv[0], nv[1], nv[2], nv[3]});
             }

@@ -276,6 +276,21 @@ __device__ __forceinline__ void st1_global(float* p, float v) {
   *(__attribute__((address_space(1))) float*)(p) = v;
 #endif
 }
+// ... and loads through such a pointer (the start table's source rows): global_load
+__device__ __forceinline__ F4 ld4_global(const float* p) {
+#if defined(MLDHIP_SIM)
+  return ld4(p);
+#else
+  return __builtin_bit_cast(F4, *(const __attribute__((address_space(1))) f32x4*)(p));
+#endif
+}
+__device__ __forceinline__ float ld1_global(const float* p) {
+#if defined(MLDHIP_SIM)
+  return *p;
+#else
+  return *(const __attribute__((address_space(1))) float*)(p);
+#endif
+}
 template <bool NT_>
 __device__ __forceinline__ F4 ld4_hint(const float* p) { if constexpr (NT_) return ld4_nt(p); else return ld4(p); }
 template <bool NT_>

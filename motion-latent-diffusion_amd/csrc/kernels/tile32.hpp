@@ -391,11 +391,13 @@ __device__ __forceinline__ float final_row_value(const FinalArgs& f, long long r
 
 // ETA (den_final_step_eta_kernel): x' = sqrt_ap x0 + k.c_eps eps + k.sigma z, z of (keys[b], step, d) -- every thread draws the Philox quad of its
 // element and keeps its own of the four (the quad's other lanes draw the same call: no exchange)
-template <bool ETA>
+// FROM (den_final_step_from_kernel, den_final_step_eta_from_kernel; mldhip_sample_many_from): a motion whose first step lies behind `step` keeps its latent and
+// stores no trajectory row -- a select on the stored value (block-uniform: one block per motion), the step's arithmetic is what it is without it.
+template <bool ETA, bool FROM = false>
 __device__ __forceinline__ void den_final_step_body(const FinalArgs& f, float* __restrict__ lat, float* __restrict__ X0,
                                                     const float* __restrict__ pe0, const float* __restrict__ t1_next,
                                                     int B, float guidance, const DdimCoef& c, const NoiseKey* __restrict__ keys, int step, DdimEta k,
-                                                    const TrajRow* __restrict__ traj) {
+                                                    const TrajRow* __restrict__ traj, const StartRow* __restrict__ starts = nullptr) {
   __shared__ float sh[4];
   const int b = blockIdx.x, d = threadIdx.x, R = 2 * B;
   const float eu = final_row_value(f, b, d, sh);
@@ -414,8 +416,13 @@ __device__ __forceinline__ void den_final_step_body(const FinalArgs& f, float* _
   } else {
     xn = c.sqrt_ap * x0 + c.sqrt_1map * eps;
   }
+  bool hold = false;
+  if constexpr (FROM) {
+    hold = step < starts[b].first_step;
+    xn = hold ? x : xn;
+  }
   lat[(long long)b * 256 + d] = xn;
-  if (traj) {                          // mldhip_sample_many_traj: prev_sample of this step to the motion's trajectory row (block-uniform test)
+  if (traj && !hold) {                 // mldhip_sample_many_traj: prev_sample of this step to the motion's trajectory row (block-uniform test)
     const TrajRow tr = traj[b];
     if (tr.row0) st1_global(tr.row0 + (long long)step * tr.step_stride + d, xn);
   }
@@ -440,6 +447,20 @@ __global__ __launch_bounds__(256) void den_final_step_eta_kernel(FinalArgs f, fl
                                                                  int B, float guidance, DdimCoef c, const NoiseKey* __restrict__ keys, int step, DdimEta k,
                                                                  const TrajRow* __restrict__ traj) {
   den_final_step_body<true>(f, lat, X0, pe0, t1_next, B, guidance, c, keys, step, k, traj);
+}
+
+__global__ __launch_bounds__(256) void den_final_step_from_kernel(FinalArgs f, float* __restrict__ lat, float* __restrict__ X0,
+                                                                  const float* __restrict__ pe0, const float* __restrict__ t1_next,
+                                                                  int B, float guidance, DdimCoef c, const TrajRow* __restrict__ traj, int step,
+                                                                  const StartRow* __restrict__ starts) {
+  den_final_step_body<false, true>(f, lat, X0, pe0, t1_next, B, guidance, c, nullptr, step, DdimEta{0.f, 0.f}, traj, starts);
+}
+
+__global__ __launch_bounds__(256) void den_final_step_eta_from_kernel(FinalArgs f, float* __restrict__ lat, float* __restrict__ X0,
+                                                                      const float* __restrict__ pe0, const float* __restrict__ t1_next,
+                                                                      int B, float guidance, DdimCoef c, const NoiseKey* __restrict__ keys, int step, DdimEta k,
+                                                                      const TrajRow* __restrict__ traj, const StartRow* __restrict__ starts) {
+  den_final_step_body<true, true>(f, lat, X0, pe0, t1_next, B, guidance, c, keys, step, k, traj, starts);
 }
 
 // Stand-alone MldDenoiser.forward output: out[r] = LN_final(LN2(...)) for the R token-0 rows.  grid = R.

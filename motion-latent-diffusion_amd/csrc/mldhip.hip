@@ -416,6 +416,36 @@ int mldhip_sample_many_traj(mldhip_handle* e, const mldhip_request* reqs, const 
   return sample_many_impl(e, reqs, nreq, (hipStream_t)stream_, eta_on(e) ? keys : nullptr, any ? traj_out_dev : nullptr);
 }
 
+int mldhip_sample_many_from(mldhip_handle* e, const mldhip_request* reqs, const mldhip_noise_key* keys, const mldhip_start* starts, float* const* traj_out_dev,
+                            int32_t nreq, void* stream_) {
+  if (!e) return MLDHIP_EINVAL;
+  bool any = false;
+  for (int i = 0; starts && nreq >= 1 && nreq <= 64 && i < nreq; ++i) any = any || starts[i].src_latents_dev || starts[i].first_step != 0 || starts[i].noised != 0;
+  // no source anywhere (and nothing else set): the call IS mldhip_sample_many_traj -- same checks, same path, same captured graphs
+  if (!any) return mldhip_sample_many_traj(e, reqs, keys, traj_out_dev, nreq, stream_);
+  DeviceGuard dg(e->device);
+  if (!reqs) return e->fail(MLDHIP_EINVAL, "1..64 requests expected");
+  if (is_novae(e)) return e->fail(MLDHIP_EINVAL, "mldhip_sample_many_from: the diffusion-only variant has no latent to start from (its loop state is the raw motion [B, T, nfeats])");
+  const int n = e->cfg.num_inference_steps;
+  bool traj = false;
+  for (int i = 0; i < nreq; ++i) {
+    const mldhip_start& s = starts[i];
+    if (s.noised != 0 && s.noised != 1) return e->fail(MLDHIP_EINVAL, "starts[%d].noised = %d (0: a clean source, 1: the loop state at first_step)", i, (int)s.noised);
+    if (s.first_step < 0 || s.first_step >= n) return e->fail(MLDHIP_EINVAL, "starts[%d].first_step = %d outside [0, num_inference_steps = %d)", i, (int)s.first_step, n);
+    if (!s.src_latents_dev && s.first_step != 0) return e->fail(MLDHIP_EINVAL, "starts[%d]: first_step = %d without a source (a start from noise begins at step 0)", i, (int)s.first_step);
+    if (!s.src_latents_dev && s.noised != 0) return e->fail(MLDHIP_EINVAL, "starts[%d]: noised = 1 without a source", i);
+    if (reinterpret_cast<uintptr_t>(s.src_latents_dev) % 16) return e->fail(MLDHIP_EINVAL, "starts[%d].src_latents_dev is not 16-byte aligned (the rows are read four floats at a time)", i);
+    if (traj_out_dev) {
+      traj = traj || traj_out_dev[i];
+      if (reinterpret_cast<uintptr_t>(traj_out_dev[i]) % 16) return e->fail(MLDHIP_EINVAL, "traj_out_dev[%d] is not 16-byte aligned (the rows are stored four floats at a time)", i);
+    }
+  }
+  if (eta_on(e) && !keys) return e->fail(MLDHIP_EINVAL, "keys is NULL on a handle with eta > 0 (one mldhip_noise_key per request)");
+  for (int i = 0; keys && i < nreq; ++i)
+    if (keys[i].first_index < 0) return e->fail(MLDHIP_EINVAL, "keys[%d].first_index %lld is negative", i, (long long)keys[i].first_index);
+  return sample_many_impl(e, reqs, nreq, (hipStream_t)stream_, eta_on(e) ? keys : nullptr, traj ? traj_out_dev : nullptr, starts);
+}
+
 int mldhip_sample(mldhip_handle* e, const float* text_emb_dev, const float* init_latents_dev, const int32_t* lengths_host,
                   int32_t B, float* latents_out_dev, float* feats_out_dev, float* joints_out_dev, void* stream_) {
   if (!e) return MLDHIP_EINVAL;

@@ -52,6 +52,11 @@ class NoiseKey(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("first_index", C.c_int64)]
 
 
+class Start(C.Structure):
+    """Mirror of ``mldhip_start`` (include/mldhip.h): where the motions of one request enter the reverse loop (``mldhip_sample_many_from``)."""
+    _fields_ = [("src_latents_dev", C.c_void_p), ("first_step", C.c_int32), ("noised", C.c_int32)]
+
+
 class NumericInfo(C.Structure):
     """Mirror of ``mldhip_numeric_info`` (include/mldhip.h, "Range contract" of the split-f16 mode)."""
     _fields_ = [("struct_size", C.c_int32), ("probed", C.c_int32), ("loop_split_ok", C.c_int32), ("decode_split_ok", C.c_int32),
@@ -84,6 +89,8 @@ _SYMBOLS = {
     "mldhip_sample_many": (C.c_int, [C.c_void_p, C.POINTER(Request), C.c_int32, C.c_void_p]),
     "mldhip_sample_many_seeded": (C.c_int, [C.c_void_p, C.POINTER(Request), C.POINTER(NoiseKey), C.c_int32, C.c_void_p]),
     "mldhip_sample_many_traj": (C.c_int, [C.c_void_p, C.POINTER(Request), C.POINTER(NoiseKey), C.POINTER(C.c_void_p), C.c_int32, C.c_void_p]),
+    "mldhip_sample_many_from": (C.c_int, [C.c_void_p, C.POINTER(Request), C.POINTER(NoiseKey), C.POINTER(Start), C.POINTER(C.c_void_p), C.c_int32,
+                                          C.c_void_p]),
     "mldhip_denoiser_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "mldhip_sample_action": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
@@ -276,6 +283,23 @@ class Engine:
         tr = (C.c_void_p * len(requests))(*[_ptr(q.get("traj_out")) or None for q in requests])
         self._check(self.lib.mldhip_sample_many_traj(self._h, arr, ks, tr, len(requests), stream))
 
+    def sample_many_from(self, requests: Sequence[dict], keys: Optional[Sequence] = None, stream: int = 0):
+        """``sample_many_traj`` whose requests may enter the reverse loop at a later step (mldhip_sample_many_from).  A request dict may carry
+        ``src_latents`` ([B_i, latent_size, latent_dim]), ``first_step`` (0 .. steps - 1, default 0) and ``noised`` (default 0): with ``noised`` 0 the
+        source is a clean latent that is noised with ``init_latents`` to the first step's timestep (diffusers' add_noise); with 1 it already is the
+        loop state in front of ``first_step`` (e.g. row ``first_step - 1`` of a trajectory) and ``init_latents`` may be None.  Steps below
+        ``first_step`` are not run for the request's motions and their trajectory rows are left untouched.  Without any ``src_latents`` the call is
+        ``sample_many_traj``."""
+        if not hasattr(self.lib, "mldhip_sample_many_from"):
+            raise MldHipError(-2, "this libmldhip has no mldhip_sample_many_from")
+        if keys is not None and len(keys) != len(requests):
+            raise ValueError("one (seed, first_index) key per request")
+        arr, keep = self._requests(requests)
+        ks = None if keys is None else (NoiseKey * len(keys))(*[NoiseKey(int(s) & 0xFFFFFFFFFFFFFFFF, int(f)) for s, f in keys])
+        tr = (C.c_void_p * len(requests))(*[_ptr(q.get("traj_out")) or None for q in requests])
+        st = (Start * len(requests))(*[Start(_ptr(q.get("src_latents")) or None, int(q.get("first_step", 0)), int(q.get("noised", 0))) for q in requests])
+        self._check(self.lib.mldhip_sample_many_from(self._h, arr, ks, st, tr, len(requests), stream))
+
     def _requests(self, requests: Sequence[dict]):
         arr = (Request * len(requests))()
         keep = []
@@ -288,7 +312,7 @@ class Engine:
                 acts = (C.c_int32 * len(q["actions"]))(*[int(x) for x in q["actions"]])
                 keep.append(acts)
                 r.actions_host = acts
-            r.init_latents_dev = _ptr(q["init_latents"]) or None
+            r.init_latents_dev = _ptr(q.get("init_latents")) or None
             r.latents_out_dev = _ptr(q.get("latents_out")) or None
             r.feats_out_dev = _ptr(q.get("feats_out")) or None
             r.joints_out_dev = _ptr(q.get("joints_out")) or None

@@ -133,8 +133,12 @@ class MLD(nn.Module):
     # ------------------------------------------------------------------ fused path
     @torch.no_grad()
     def sample(self, text_emb: torch.Tensor, lengths: List[int], init_latents: Optional[torch.Tensor] = None, seed: Optional[int] = None,
-               first_index: int = 0, return_trajectory: bool = False):
+               first_index: int = 0, return_trajectory: bool = False, src_latents: Optional[torch.Tensor] = None, first_step: int = 0,
+               noised: bool = False):
         """text_emb [2B, 1, 768] (uncond half first) -> (joints [B,T,njoints,3], feats [B,T,nfeats], latents [B,1,D]) on device.
+        src_latents [B, 1, D] (mldhip_sample_many_from): the loop starts at scheduler step `first_step` from the source noised with init_latents to
+        that step's timestep (`noised` False), or from the source as it is (`noised` True: it already is the loop state there); trajectory rows
+        below first_step are left as allocated.
         eta > 0: the step noise of motion m is the engine's Philox stream keyed (seed, first_index + m); `seed` None = drawn from torch's
         generator.  return_trajectory: a fourth result, the latents after every scheduler step [steps, B, D] (mldhip_sample_many_traj; its last
         row is `latents`)."""
@@ -154,6 +158,13 @@ class MLD(nn.Module):
         feats = torch.empty(B, T, self.nfeats, device=dev)
         joints = torch.empty(B, T, self.njoints, 3, device=dev)
         seed = self._noise_seed(seed)
+        if src_latents is not None:
+            req = dict(text_emb=text_emb, init_latents=init_latents, lengths=lengths, latents_out=lat, feats_out=feats, joints_out=joints,
+                       src_latents=src_latents.to(dev).float().contiguous(), first_step=int(first_step), noised=int(bool(noised)))
+            if return_trajectory:
+                req["traj_out"] = self._traj_buffer(eng, B, dev)
+            eng.sample_many_from([req], None if seed is None else [(seed, int(first_index))], _engine.current_stream_handle(text_emb))
+            return (joints, feats, lat, req["traj_out"]) if return_trajectory else (joints, feats, lat)
         if return_trajectory:
             traj = self._traj_buffer(eng, B, dev)
             eng.sample_many_traj([dict(text_emb=text_emb, init_latents=init_latents, lengths=lengths, latents_out=lat, feats_out=feats,
@@ -169,7 +180,7 @@ class MLD(nn.Module):
 
     @torch.no_grad()
     def sample_many(self, requests, init_latents=None, pipeline: bool = False, seed: Optional[int] = None, first_index: int = 0,
-                    return_trajectory: bool = False):
+                    return_trajectory: bool = False, src_latents=None, first_step=None, noised=None):
         """Several independent text-to-motion requests as ONE engine call (``mldhip_sample_many``: one reverse-diffusion chain +
         one decode over all of them; the engine needs ``max_batch >= total motions``).  `requests` = [(text_emb [2B_i,1,768],
         lengths_i), ...]; returns [(joints_i, feats_i, latents_i), ...] on device, each shaped as ``sample`` would return it.
@@ -179,7 +190,10 @@ class MLD(nn.Module):
         for it, with the decode of request k overlapped with the reverse loop of request k + 1 (bs-64 requests: 7.0 instead of 8.0 ms each).
 
         ``return_trajectory=True``: every result tuple gets a fourth entry, the request's latents after every scheduler step [steps, B_i, D]
-        (mldhip_sample_many_traj; such a call runs as one chain, also with ``pipeline=True``)."""
+        (mldhip_sample_many_traj; such a call runs as one chain, also with ``pipeline=True``).
+
+        ``src_latents`` / ``first_step`` / ``noised``: one entry per request (a tensor [B_i, 1, D] or None; an int; a bool) -- where each request
+        enters the reverse loop (mldhip_sample_many_from, see ``sample``); such a call runs as one chain as well."""
         if self.vae_type == "no" or self.condition == "action":
             raise NotImplementedError("sample_many serves the text-to-motion latent model")
         eng = self._engine()
@@ -201,6 +215,9 @@ class MLD(nn.Module):
             joints = torch.empty(B, T, self.njoints, 3, device=dev)
             keep.append((text_emb, lat0))
             reqs.append(dict(text_emb=text_emb, init_latents=lat0, lengths=lengths, latents_out=lat, feats_out=feats, joints_out=joints))
+            if src_latents is not None and src_latents[i] is not None:
+                reqs[-1].update(src_latents=src_latents[i].to(dev).float().contiguous(), first_step=int(first_step[i]) if first_step is not None else 0,
+                                noised=int(bool(noised[i])) if noised is not None else 0)
             if return_trajectory:
                 reqs[-1]["traj_out"] = self._traj_buffer(eng, B, dev)
                 outs.append((joints, feats, lat, reqs[-1]["traj_out"]))
@@ -210,7 +227,9 @@ class MLD(nn.Module):
             eng.set_option("many_pipeline", 1)
         seed = self._noise_seed(seed)
         try:
-            if return_trajectory:
+            if any("src_latents" in q for q in reqs):
+                eng.sample_many_from(reqs, None if seed is None else self._keys(seed, reqs, first_index), stream)
+            elif return_trajectory:
                 eng.sample_many_traj(reqs, None if seed is None else self._keys(seed, reqs, first_index), stream)
             elif seed is None:
                 eng.sample_many(reqs, stream)
@@ -376,6 +395,30 @@ class MLD(nn.Module):
         joints = self.feats2joints(feats_rst.detach())
         joints_ref = self.feats2joints(feats_ref.detach().contiguous())
         return remove_padding(joints.cpu(), length), remove_padding(joints_ref.cpu(), length)
+
+    @torch.no_grad()
+    def edit(self, batch, strength: float, init_latents: Optional[torch.Tensor] = None, seed: Optional[int] = None, sample_mean: bool = True):
+        """Motion-to-motion under a new prompt, as diffusers' image-to-image pipelines do it: batch {"motion" [B, T, nfeats], "text", "length"} ->
+        joints per motion (as ``forward`` returns them).  The motion is encoded (``HipMldVae.encode``; the distribution's mean, or its sample with
+        ``sample_mean=False``), noised to scheduler step ``first_step = n - min(int(n * strength), n)`` with ``init_latents`` (default: torch.randn) and
+        denoised from there under batch["text"] in ONE mldhip_sample_many_from call: strength 1 runs every step, strength 0.3 the last 30 % of them,
+        strength 0 (first_step == n) returns the reconstruction without a loop."""
+        if not self.fused or self.vae_type == "no" or self.condition == "action":
+            raise NotImplementedError("edit serves the fused text-to-motion latent model")
+        motion, texts, lengths = batch["motion"], list(batch["text"]), [int(x) for x in batch["length"]]
+        z, dist = self.vae.encode(motion, lengths)
+        src = (dist.loc if sample_mean else z).permute(1, 0, 2).contiguous()            # [B, latent_size, D]
+        n = int(self.cfg.model.scheduler.num_inference_timesteps)
+        first_step = n - min(int(n * float(strength)), n)
+        if first_step == n:
+            feats = self.vae.decode(src.permute(1, 0, 2).contiguous(), lengths)
+            return remove_padding(self.feats2joints(feats.detach()).cpu(), lengths)
+        if self.do_classifier_free_guidance:                                    # mld.py:224-230: uncond half first
+            texts = [""] * len(texts) + ([""] * len(texts) if self.condition == "text_uncond" else texts)
+        text_emb = self.text_encoder(texts).to(src.device)
+        noise_kw = {} if self.eta == 0.0 else {"seed": seed}
+        joints, _, _ = self.sample(text_emb, lengths, init_latents, src_latents=src, first_step=first_step, **noise_kw)
+        return remove_padding(joints.detach().cpu(), lengths)
 
     @torch.no_grad()
     def _diffusion_reverse(self, encoder_hidden_states, lengths=None, init_latents: Optional[torch.Tensor] = None,
