@@ -466,12 +466,15 @@ def sample_novae(ops, sd_den, text_emb, init_latents, lengths, step_noise, mean=
 PHILOX_M0, PHILOX_M1, PHILOX_W0, PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
 
 
-def philox_normal(n, seed, step):
+def philox_normal(n, seed, step, first=0):
     """The engine's counter-based N(0,1) stream (kernels/novae.hpp: Philox4x32-10 + Box-Muller), numpy restatement:
-    element e belongs to counter (e // 4, step), key = seed; uniform = (x >> 8 + 0.5) / 2^24."""
+    element e belongs to counter (e // 4, step), key = seed; uniform = (x >> 8 + 0.5) / 2^24.  Returns elements first .. first + n - 1
+    (first a multiple of 4, below 2^66: the quad counter is 64 bits)."""
+    if first < 0 or first % 4:
+        raise ValueError("first must be a non-negative multiple of 4")
     nq = (n + 3) // 4
-    c = [np.arange(nq, dtype=np.uint64) & 0xFFFFFFFF, np.arange(nq, dtype=np.uint64) >> 32,
-         np.full(nq, step, np.uint64), np.zeros(nq, np.uint64)]
+    quad = (np.arange(nq, dtype=np.uint64) + np.uint64(first // 4))
+    c = [quad & np.uint64(0xFFFFFFFF), quad >> np.uint64(32), np.full(nq, step, np.uint64), np.zeros(nq, np.uint64)]
     k0, k1 = seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF
     for _ in range(10):
         p0, p1 = PHILOX_M0 * c[0], PHILOX_M1 * c[2]

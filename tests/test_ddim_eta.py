@@ -36,7 +36,7 @@ def ddim_eta_step_np(eps, t, x, z, eta, sch):
 
 def keyed_noise(seed, first, B, step):
     """z of motions first .. first + B - 1 at scheduler step `step` (the Noise contract): [B, 1, 256]"""
-    return O.philox_normal((first + B) * 256, seed, step)[first * 256:].reshape(B, 1, 256)
+    return O.philox_normal(B * 256, seed, step, first=first * 256).reshape(B, 1, 256)
 
 
 def reverse_eta_np(sdd, text_emb, init_latents, steps, eta, keys_per_motion, guidance=7.5):

@@ -34,13 +34,11 @@ def oracle_eta(text_emb, init_latents, lengths, eta, seed, indices, steps=50, gu
     sch = O.DDIMSchedule()
     lat = init_latents.astype(f32)
     B = lat.shape[0]
-    idx = np.asarray(indices, np.int64)
-    rows = (idx[:, None] * 256 + np.arange(256)[None, :])
     for i, t in enumerate(sch.set_timesteps(steps)):
         e = np.asarray(O.denoiser_forward(ops, sd, np.concatenate([lat, lat], 0), t, text_emb, 4))
         u, c = e[:B], e[B:]
         eps = u + f32(guidance) * (c - u)
-        z = O.philox_normal(int(idx.max() + 1) * 256, seed, i)[rows].reshape(B, 1, 256)
+        z = np.stack([O.philox_normal(256, seed, i, first=int(k) * 256) for k in indices]).reshape(B, 1, 256)
         prev = int(t) - sch.num_train_timesteps // steps
         a_t = f32(sch.alphas_cumprod[int(t)])
         a_p = f32(sch.alphas_cumprod[prev]) if prev >= 0 else f32(sch.final_alpha_cumprod)
