@@ -141,6 +141,13 @@ typedef struct mldhip_config {
   int32_t clip_vocab;           /* vocab_size = 49408 */
   int32_t clip_ctx;             /* max_position_embeddings = 77 */
   int32_t clip_max_prompts;     /* capacity: prompts per mldhip_text_encode call; 0 (default) = 2 x max_batch (one classifier-free-guidance batch) */
+  /* ---- the optional T2M evaluator towers (mldhip_t2m_motion_embed / mldhip_t2m_text_embed below; MLDHIP_ABI_VERSION stays 8: callers detect the feature by
+   * the presence of the two symbols).  Read only when struct_size covers them (a caller's struct that ends behind clip_max_prompts means no evaluators).
+   * With t2m_eval = 1 mldhip_create refuses MLDHIP_PREC_BF16, nfeats < 8 and nfeats > 292 (the first convolution's GEMM is built for up to 288 input channels). */
+  int32_t t2m_eval;             /* 0 (default) = no evaluators: no weights, no workspace, every t2m_* key ignored; 1 = both towers */
+  int32_t t2m_max_motions;      /* capacity: motions per mldhip_t2m_motion_embed call and captions per mldhip_t2m_text_embed call; 0 (default) = 2 x max_batch
+                                 * (a batch's generated and ground-truth motions in one call) */
+  int32_t t2m_max_words;        /* capacity: words per caption (L of mldhip_t2m_text_embed); 0 (default) = 32 */
 } mldhip_config;
 
 enum { MLDHIP_COND_TEXT = 0, MLDHIP_COND_ACTION = 1 };
@@ -334,6 +341,12 @@ int mldhip_set_option(mldhip_handle* h, const char* name, int64_t value);
  * small-weights limit above: fc2's weights sit at 3e-4, where the low half is a subnormal -- reads 6.1e-5 (4.4e-5 on the one-layer simulator tower, where plain
  * reads 2.8e-6) and falls back; left split it ends 63 x e32 from fp64 with finite outputs and a silent counter.  fc1 x 2^16 (hidden activation 2.4e5) reads inf and
  * falls back; with "range_probe" 0 it returns NaN rows, all of them counted.
+ * The T2M evaluator towers (t2m_eval = 1) are a fifth stage.  PROBE: on an F16X3 handle whose evaluator groups are loaded, finalize embeds four seeded motions
+ * (T = min(64, max_frames), lengths 64 / 37 / 20 / 4 clipped to T, unit-normal features, no renorm) and four seeded captions (t2m_max_words words at most) on the
+ * split-f16 towers and on the exact-fp32 towers of the same handle, and multiplies 16 seeded state rows (uniform in (-1, 1)) with W_hh^T of every tower and direction,
+ * split image against fp32 (the embeddings of unit-normal probe rows cannot see a W_hh whose split image lost its precision -- weights near 1e-5, both halves half subnormals
+ * -- because the input-side gate terms are O(1) there; a caller's rows may differ): probe_err_eval = the largest max|split - fp32| / max|fp32| of these readings.  FALLBACK: above
+ * MLDHIP_PROBE_TOL (or not finite) eval_split_ok = 0 and both towers run their fp32 kernels: results equal MLDHIP_PREC_F32's to the bit.
  * The other modes: F32 has no such limits; BF16 is a reported-only mode whose errors bench.py prints. */
 #define MLDHIP_PROBE_TOL 6e-6f
 #define MLDHIP_PROBE_TOL_HALF 3e-5f
@@ -354,6 +367,9 @@ typedef struct mldhip_numeric_info {
   /* ---- ABI 8: the CLIP text tower's stage.  Written only when struct_size covers them (an ABI-7 caller's smaller struct is accepted and gets the fields above). */
   int32_t text_split_ok;      /* 1: mldhip_text_encode multiplies on split-f16 MFMAs; 0: fell back to exact fp32, or no tower / another mode */
   float probe_err_text;       /* the tower stage's err (-1: not probed / no tower) */
+  /* ---- the T2M evaluator towers' stage.  Written only when struct_size covers them (the struct that ends behind probe_err_text is accepted). */
+  int32_t eval_split_ok;      /* 1: the evaluator towers multiply on split-f16 MFMAs; 0: fell back to exact fp32, or no evaluators / another mode */
+  float probe_err_eval;       /* the evaluator stage's err: the larger of the two towers' (-1: not probed / no evaluators) */
 } mldhip_numeric_info;
 /* Synchronises the device (it reads the counter), fills *out and resets nonfinite_values.  No reference counterpart. */
 int mldhip_numeric_status(mldhip_handle* h, mldhip_numeric_info* out);
@@ -564,6 +580,52 @@ int mldhip_ddim_step_eta(mldhip_handle* h, const float* eps_dev, int32_t timeste
  * Returns MLDHIP_EINVAL for P > clip_max_prompts, an id outside [0, clip_vocab) or eos_pos outside [0, clip_ctx); MLDHIP_ESTATE when the handle has no
  * tower (clip_layers = 0), the tower's weight group is absent, or the handle is not finalized. */
 int mldhip_text_encode(mldhip_handle* h, const int32_t* ids_host, const int32_t* eos_pos_host, int32_t P, float* text_emb_out_dev, void* stream);
+
+/* The T2M evaluator towers (handles created with t2m_eval = 1).  Replaces: the evaluator half of MLD.t2m_eval (mld/models/modeltype/mld.py:675-697):
+ * renorm4t2m, MovementConvEncoder -> MotionEncoderBiGRUCo for motions, TextEncoderBiGRUCo for captions (mld/models/architectures/t2m_motionenc.py,
+ * t2m_textenc.py), at the released evaluators' widths (configs/base.yaml: movement 512 / 512, motion GRU 1024 -> 512, word 300, POS one-hot 15, text GRU
+ * 512 -> 512, unit length 4) -- the only widths the kernels are built for.
+ *
+ * WEIGHTS.  Two more optional all-or-nothing groups under their checkpoint key names (a wrong shape is MLDHIP_EINVAL, mldhip_missing_keys reports a half-loaded
+ * group; with t2m_eval = 0 every t2m_* key stays accepted and ignored, mis-shaped ones included):
+ *   motion group: t2m_moveencoder.main.{0,3}.{weight,bias} ([512][nfeats - 4][4], [512][512][4]), t2m_moveencoder.out_net.{weight,bias},
+ *                 t2m_motionencoder.input_emb.{weight,bias}, t2m_motionencoder.gru.{weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0} and their four
+ *                 *_reverse tensors, t2m_motionencoder.hidden [2][1][1024], t2m_motionencoder.output_net.{0,1,3}.{weight,bias}, mean_eval, std_eval [nfeats];
+ *   text group:   t2m_textencoder.pos_emb.{weight,bias}, .input_emb.{weight,bias}, .gru.* (the same eight), .hidden [2][1][512], .output_net.{0,1,3}.{weight,bias}.
+ *
+ * MATH, motion tower.  feats [B][T][nfeats], lengths [B].
+ *   renorm (renorm = 1; needs mean / std): g = (f std + mean - mean_eval) / std_eval on ALL T frames.  PADDED-FRAME RULE: a padded frame (t >= len) holds 0 in f
+ *     and therefore a non-zero constant in g; the convolutions of the last valid steps read those rows; before frame 0 and beyond frame T - 1 the convolutions pad
+ *     with true zeros.  So a motion's embedding depends on T exactly as it does in the reference (equal for any two T >= len + 7).  renorm = 0: the rows already are in
+ *     the evaluators' normalisation (eval_gt).
+ *   columns 0 .. nfeats - 5; Conv1d(nfeats - 4 -> 512, k 4, s 2, p 1), LeakyReLU(0.2), Conv1d(512 -> 512, 4, 2, 1), LeakyReLU(0.2), Linear(512, 512): floor(T / 4) rows
+ *     per motion (dropout is identity);
+ *   Linear(512 -> 1024); a bidirectional one-layer GRU, H = 1024, initial state hidden[dir] for every motion, packed-sequence semantics with m_len = len / 4
+ *     (floor): the forward direction runs rows 0 .. m_len - 1, the backward direction m_len - 1 .. 0; a motion's state is untouched outside its own steps;
+ *   cat(h_fwd, h_bwd) -> Linear(2048 -> 1024), LayerNorm, LeakyReLU(0.2), Linear(1024 -> 512).
+ *   GRU cell (PyTorch's; gate order r | z | n in the stacked weights): r = s(W_ir x + b_ir + W_hr h + b_hr), z likewise, n = tanh(W_in x + b_in + r (W_hn h + b_hn)),
+ *     h' = (1 - z) n + z h.
+ * MATH, text tower.  word_embs [B][L][300], pos_ohot [B][L][15], text_lengths [B]: x = word + Linear(15 -> 300)(pos); Linear(300 -> 512); the same GRU at H = 512
+ *   with packed lengths text_lengths; the same head (1024 -> 512, LayerNorm, LeakyReLU, 512 -> 512).
+ * Any order of lengths is taken and rows come back in the caller's order (the reference sorts only because pack_padded_sequence demands it).  A motion's or
+ * caption's embedding is bit-identical alone and inside any batch (at the same T / L): one GEMM tile shape and one recurrence kernel at every row count.
+ *
+ * KERNELS.  kernels/gru.hpp: the staging kernels (renorm + the convolution's zero rows; word + POS linear), the recurrence -- ONE launch per time step (at most 49
+ * for 196 frames), both directions and all motions, h W_hh^T on MFMAs with the gate math, the per-motion step mask and the state update fused, state double
+ * buffered -- and LayerNorm + LeakyReLU.  Every linear and both convolutions (as GEMMs over tap-major re-laid weights: lda = 2 C, K = 4 C) and the input-side GRU
+ * products of both directions (one GEMM, b_hr / b_hz folded into its bias) run on the staged 64 x 128 GEMM tile of kernels/gemm.hpp with its EPI = 2 epilogue.
+ * MLDHIP_PREC_F32: exact fp32 MFMAs; MLDHIP_PREC_F16X3: split-f16 products (pre-split weight image) unless finalize's probe moved the towers to fp32 ("Range
+ * contract", eval_split_ok).  More than 256 motions are processed in chunks of 256 (workspace bound; the numbers do not depend on it).
+ *
+ * Both calls are stream-ordered and issued eagerly (no hipGraph), lengths reach the kernels through an engine-owned table uploaded with the call, non-finite
+ * outputs go into the sticky counter.  MLDHIP_EINVAL: B outside 1 .. t2m_max_motions, T > max_frames, a length < 4 (m_len 0: PyTorch refuses an empty packed
+ * sequence) or > T, a text length outside 1 .. L, L > t2m_max_words, null pointers, renorm outside {0, 1}.  MLDHIP_ESTATE: no evaluators on the handle, the
+ * group (renorm = 1: or mean / std) not loaded, the handle not finalized. */
+int mldhip_t2m_motion_embed(mldhip_handle* h, const float* feats_dev /*[B,T,nfeats]*/, const int32_t* lengths_host, int32_t B, int32_t T,
+                            int32_t renorm /* 1: renorm4t2m first (needs mean/std); 0: already in evaluator normalisation (eval_gt's switch) */,
+                            float* emb_out_dev /*[B,512]*/, void* stream);
+int mldhip_t2m_text_embed(mldhip_handle* h, const float* word_embs_dev /*[B,L,300]*/, const float* pos_ohot_dev /*[B,L,15]*/,
+                          const int32_t* text_lengths_host, int32_t B, int32_t L, float* emb_out_dev /*[B,512]*/, void* stream);
 
 /* Replaces: HumanML3DDataModule.feats2joints (mld/data/HumanML3D.py:41-45 -> recover_from_ric,
  * mld/data/humanml/scripts/motion_process.py:415-432).  feats [B,T,nfeats] -> joints [B,T,njoints,3]. */

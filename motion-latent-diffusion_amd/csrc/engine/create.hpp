@@ -127,6 +127,13 @@ const char* config_error(const mldhip_config* cfg) {
     if (cfg->precision == MLDHIP_PREC_BF16) return "text tower: MLDHIP_PREC_BF16 is refused (exact fp32 or split-f16 only)";
     if ((long long)cfg->clip_max_prompts * cfg->clip_ctx > (1 << 20)) return "text tower: clip_max_prompts x clip_ctx must be <= 2^20 rows";
   }
+  if (cfg->t2m_eval != 0 && cfg->t2m_eval != 1) return "t2m_eval must be 0 (no evaluators) or 1 (both T2M evaluator towers)";
+  if (cfg->t2m_eval) {             // the T2M evaluator towers (mldhip_t2m_motion_embed / mldhip_t2m_text_embed)
+    if (cfg->precision == MLDHIP_PREC_BF16) return "evaluator towers: MLDHIP_PREC_BF16 is refused (exact fp32 or split-f16 only)";
+    if (cfg->nfeats < 8 || cfg->nfeats - 4 > kEvalConvC) return "evaluator towers: nfeats must be 8 .. 292 (the first convolution's GEMM is built for up to 288 input channels)";
+    if (cfg->t2m_max_motions < 1 || cfg->t2m_max_motions > (1 << 20)) return "evaluator towers: t2m_max_motions must be 1 .. 2^20";
+    if (cfg->t2m_max_words < 1 || cfg->t2m_max_words > 1024) return "evaluator towers: t2m_max_words must be 1 .. 1024";
+  }
   return nullptr;
 }
 
@@ -201,6 +208,20 @@ void carve_clip(E* e, Carver& want) {
   want(&e->cX, R * W); want(&e->cLN, R * W); want(&e->cQKV, R * 3 * W); want(&e->cAO, R * W); want(&e->cFF, R * F);
   want(&e->cE0, Pm * W); want(&e->cE1, Pm * W);
   want(&e->cTab, 2 * R + 4 * Pm);      // ints: token id and position per row; row offset, row count and EOS row per unique prompt; unique index per prompt
+}
+
+// workspace of the T2M evaluator towers (engine/path_eval.hpp), carved only when t2m_eval = 1: sized for one chunk of kEvalChunk motions x max_frames frames /
+// captions x t2m_max_words words
+void carve_eval(E* e, Carver& want) {
+  const auto& c = e->cfg;
+  if (!c.t2m_eval) return;
+  const size_t Bc = (size_t)std::min(c.t2m_max_motions, kEvalChunk), TP = (size_t)eval_tp(c.max_frames), R1 = TP / 2, R2 = TP / 4;
+  const size_t rows = Bc * std::max<size_t>(R2, (size_t)c.t2m_max_words);
+  want(&e->vG0, (Bc * TP + 2) * kEvalConvC); want(&e->vG1, (Bc * R1 + 2) * kEvalMove);
+  want(&e->vA, rows * kEvalMotionH); want(&e->vB, rows * kEvalMove);
+  want(&e->vGi, std::max<size_t>(Bc * R2 * 6 * kEvalMotionH, Bc * (size_t)c.t2m_max_words * 6 * kEvalTextH));
+  want(&e->vH0, Bc * 2 * kEvalMotionH); want(&e->vH1, Bc * 2 * kEvalMotionH); want(&e->vHead, Bc * kEvalMotionH);
+  want(&e->vTab, 3 * Bc);      // ints: rows per motion behind each convolution, GRU steps per motion
 }
 
 // Kernels launched with more dynamic LDS than the default limit register their size once per process and device (tests/test_cabi.py compares this list
@@ -370,6 +391,7 @@ int create_engine(const mldhip_config& cfg, int device, int num_cus, mldhip_hand
   if (is_novae(e)) carve_novae(e, want);
   else carve_latent(e, want);
   carve_clip(e, want);
+  carve_eval(e, want);
   const size_t Bm = cfg.max_batch;
   e->ws_floats = want.off;
   e->ctxs.resize(cfg.max_in_flight);

@@ -168,6 +168,27 @@ void gemm_clip(Ctx& c, const GemmArgs& a_, bool x3) {
   check_launch(c, "gemm_clip");
 }
 
+// The T2M evaluator towers' GEMMs (engine/path_eval.hpp) on the staged 64 x 128 tile with the EPI = 2 epilogue (bias, LeakyReLU(0.2) or nothing, masked rows
+// stored as zeros): K = 384 (the text tower's 300-wide input, padded), 512, 1024, 1152 (the first convolution: 4 taps x 288 padded channels) and 2048 (the second
+// convolution; the motion head's first linear).  ONE tile shape at every row count, like the text tower's: a motion's rows do not depend on what else is in the call.
+template <int PREC, int KCS>
+void launch_eval_staged(Ctx& c, const GemmArgs& a, dim3 grid) {
+  constexpr int lds = gemm_lds_bytes<2, 4, 2, 2>();
+  MLD_LAUNCH((gemm_kernel<2, 4, 2, 2, false, true, PREC, KCS, false, 2>), grid, dim3(512), lds, c.stream, a);
+}
+void gemm_eval(Ctx& c, const GemmArgs& a_, bool x3) {
+  GemmArgs a = a_;
+  const int K = a.K1;
+  if (x3) use_split_weights(c.e, a, PREC_F16X3);
+  const dim3 grid((a.M + 63) / 64, (a.N + 127) / 128, 1);
+#define MLD_EVAL_K(KV) \
+  if (K == KV) { if (x3) launch_eval_staged<PREC_F16X3, KV / 32>(c, a, grid); else launch_eval_staged<PREC_F32, KV / 32>(c, a, grid); } else
+  MLD_EVAL_K(384) MLD_EVAL_K(512) MLD_EVAL_K(1024) MLD_EVAL_K(1152) MLD_EVAL_K(2048)
+    c.rc = c.e->fail(MLDHIP_EINVAL, "evaluator GEMM: K=%d not in {384, 512, 1024, 1152, 2048}", K);
+#undef MLD_EVAL_K
+  check_launch(c, "gemm_eval");
+}
+
 GemmArgs lin_args(const float* A, int lda, int K, const float* W, const float* b, float* Y, int ldy, int M, int N) {
   GemmArgs g;
   g.A = A; g.lda = lda; g.K1 = K; g.W = W; g.ldw = K; g.bias = b; g.Y = Y; g.ldy = ldy; g.M = M; g.N = N;

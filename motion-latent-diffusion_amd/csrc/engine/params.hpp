@@ -141,7 +141,8 @@ size_t add_param(E* e, const std::string& key, std::vector<int64_t> shape) {
   p.offset = e->arena_floats;
   const bool enc = key.rfind("vae.encoder.", 0) == 0 || key.rfind("vae.skel_embedding.", 0) == 0 ||
                    key.rfind("vae.global_motion_token", 0) == 0 || key.rfind("vae.query_pos_encoder.", 0) == 0;
-  p.group = key.rfind("denoiser.", 0) == 0 ? 0 : enc ? 3 : key.rfind("vae.", 0) == 0 ? 1 : key.rfind("text_encoder.", 0) == 0 ? 4 : 2;
+  const bool ev_text = key.rfind("t2m_textencoder.", 0) == 0, ev_motion = !ev_text && (key.rfind("t2m_", 0) == 0 || key == "mean_eval" || key == "std_eval");
+  p.group = ev_text ? 6 : ev_motion ? 5 : key.rfind("denoiser.", 0) == 0 ? 0 : enc ? 3 : key.rfind("vae.", 0) == 0 ? 1 : key.rfind("text_encoder.", 0) == 0 ? 4 : 2;
   e->arena_floats += align_up(p.numel);
   e->index[key] = int(e->params.size());
   e->params.push_back(p);
@@ -174,9 +175,42 @@ void declare_clip_params(E* e) {
 
 // Declares every tensor the sampling path reads, in execution order.
 void declare_model_params(E* e);
+// The T2M evaluators' tensors (t2m_eval = 1) under their checkpoint names, at the released widths (the reference's configs/base.yaml).  A GRU's weight_ih_l0 and
+// weight_ih_l0_reverse are declared back to back (each a multiple of kAlign floats): together they ARE the [6H][K] weight of the one input-side GEMM of both directions.
+constexpr int kEvalMove = 512, kEvalMotionH = 1024, kEvalTextH = 512, kEvalOut = 512, kEvalWord = 300, kEvalPos = 15, kEvalUnit = 4;
+constexpr int kEvalChunk = 256;      // motions / captions per pass of a tower (workspace bound)
+constexpr int kEvalConvC = 288;      // input channels of the first convolution's GEMM (nfeats - 4 zero-padded: K = 4 x 288 = 1152)
+constexpr int kEvalTextK = 384;      // K of the text tower's input linear (300 zero-padded)
+void declare_t2m_params(E* e) {
+  const int64_t NF = e->cfg.nfeats;
+  auto lin = [&](const std::string& p, int64_t o, int64_t i) { add_param(e, p + ".weight", {o, i}); add_param(e, p + ".bias", {o}); };
+  auto gru = [&](const std::string& p, int64_t H, int64_t K) {
+    add_param(e, p + ".weight_ih_l0", {3 * H, K}); add_param(e, p + ".weight_ih_l0_reverse", {3 * H, K});
+    add_param(e, p + ".weight_hh_l0", {3 * H, H}); add_param(e, p + ".weight_hh_l0_reverse", {3 * H, H});
+    for (const char* n : {"bias_ih_l0", "bias_hh_l0", "bias_ih_l0_reverse", "bias_hh_l0_reverse"}) add_param(e, p + "." + n, {3 * H});
+  };
+  add_param(e, "t2m_moveencoder.main.0.weight", {kEvalMove, NF - 4, 4}); add_param(e, "t2m_moveencoder.main.0.bias", {kEvalMove});
+  add_param(e, "t2m_moveencoder.main.3.weight", {kEvalMove, kEvalMove, 4}); add_param(e, "t2m_moveencoder.main.3.bias", {kEvalMove});
+  lin("t2m_moveencoder.out_net", kEvalMove, kEvalMove);
+  for (int tower = 0; tower < 2; ++tower) {
+    const std::string p = tower == 0 ? "t2m_motionencoder" : "t2m_textencoder";
+    const int64_t H = tower == 0 ? kEvalMotionH : kEvalTextH;
+    if (tower == 1) lin(p + ".pos_emb", kEvalWord, kEvalPos);
+    lin(p + ".input_emb", H, tower == 0 ? kEvalMove : kEvalWord);
+    gru(p + ".gru", H, H);
+    add_param(e, p + ".hidden", {2, 1, H});
+    lin(p + ".output_net.0", H, 2 * H);
+    add_param(e, p + ".output_net.1.weight", {H}); add_param(e, p + ".output_net.1.bias", {H});
+    lin(p + ".output_net.3", kEvalOut, H);
+  }
+  add_param(e, "mean_eval", {NF});
+  add_param(e, "std_eval", {NF});
+}
+
 void declare_params(E* e) {
   declare_model_params(e);
   if (e->cfg.clip_layers > 0) declare_clip_params(e);
+  if (e->cfg.t2m_eval) declare_t2m_params(e);
 }
 void declare_model_params(E* e) {
   const auto& c = e->cfg;

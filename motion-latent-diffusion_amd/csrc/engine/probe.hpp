@@ -314,6 +314,79 @@ int probe_text(E* e, hipStream_t stream, ProbeRng& rng) {
   return MLDHIP_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- stage 5: the T2M evaluator towers
+// four seeded motions (T = min(64, max_frames), lengths 64 / 37 / 20 / 4 clipped to T: full, len % 4 = 1, a short one, a single GRU step; unit-normal rows in the
+// evaluators' normalisation, no renorm) and four seeded captions (the longest t2m_max_words allows, 3, 2 and 1 words) on the split-f16 towers and on the exact-fp32
+// towers of the same handle, then the recurrent products h . W_hh^T by themselves (below).  One tile shape and one recurrence kernel per mode at every row count: nothing to lift.
+int probe_eval(E* e, hipStream_t stream, ProbeRng& rng) {
+  const int NF = e->cfg.nfeats, NB = std::min(4, e->cfg.t2m_max_motions);
+  float worst = -1.f;
+  ProbeDev out;
+  if (out.make((size_t)NB * kEvalOut)) return e->fail(MLDHIP_EHIP, "range probe: hipMalloc");
+  std::vector<float> ha, hb;
+  if (e->group_ready[5] && e->cfg.max_frames >= kEvalUnit) {
+    const int T = std::min(64, e->cfg.max_frames);
+    const int want[4] = {64, 37, 20, 4};
+    std::vector<int32_t> lens(NB);
+    for (int b = 0; b < NB; ++b) lens[b] = std::max(kEvalUnit, std::min(want[b], T));
+    std::vector<float> hf((size_t)NB * T * NF + 1);
+    rng.fill(hf, 1.0f);
+    for (int b = 0; b < NB; ++b)
+      for (size_t i = ((size_t)b * T + lens[b]) * NF; i < (size_t)(b + 1) * T * NF; ++i) hf[i] = 0.f;      // padded frames hold zeros, as the decoder leaves them
+    ProbeDev feats;
+    if (feats.up(hf)) return e->fail(MLDHIP_EHIP, "range probe: hipMalloc");
+    for (int split = 1; split >= 0; --split) {
+      e->eval_split_ok = split != 0;
+      if (int rc = t2m_motion_embed_impl(e, feats.p, lens.data(), NB, T, 0, out.p, stream, false)) return rc;
+      if (int rc = probe_down(e, stream, out.p, (size_t)NB * kEvalOut, split ? ha : hb)) return rc;
+    }
+    worst = std::max(worst, rel_err(ha, hb));
+  }
+  if (e->group_ready[6]) {
+    const int L = std::min(20, e->cfg.t2m_max_words);
+    const int want[4] = {L, 3, 2, 1};
+    std::vector<int32_t> lens(NB);
+    for (int b = 0; b < NB; ++b) lens[b] = std::min(want[b], L);
+    std::vector<float> hw((size_t)NB * L * kEvalWord + 1), hp((size_t)NB * L * kEvalPos, 0.f);
+    rng.fill(hw, 1.0f);
+    for (int i = 0; i < NB * L; ++i) hp[(size_t)i * kEvalPos + rng.bits() % kEvalPos] = 1.f;
+    ProbeDev word, pos;
+    if (word.up(hw) || pos.up(hp)) return e->fail(MLDHIP_EHIP, "range probe: hipMalloc");
+    for (int split = 1; split >= 0; --split) {
+      e->eval_split_ok = split != 0;
+      if (int rc = t2m_text_embed_impl(e, word.p, pos.p, lens.data(), NB, L, out.p, stream, false)) return rc;
+      if (int rc = probe_down(e, stream, out.p, (size_t)NB * kEvalOut, split ? ha : hb)) return rc;
+    }
+    worst = std::max(worst, rel_err(ha, hb));
+  }
+  // (c) the recurrent products by themselves: 16 seeded state rows (uniform in (-1, 1), where a GRU state lives) times W_hh^T of every loaded tower and direction,
+  // split image against fp32, on the towers' own GEMM tile.  The embeddings above cannot see this operand on the probe's inputs: unit-normal rows make the input-side
+  // gate terms O(1), and a W_hh whose split image has lost its precision (weights near 1e-5: both halves are half subnormals, ~4e-3 relative) then moves an embedding
+  // by 1e-7 -- on a caller's rows whose input-side terms are as small as the recurrent ones it would not.  The product is held to the same bound as the outputs.
+  for (int tower = 0; tower < 2; ++tower) {
+    if (!e->group_ready[5 + tower]) continue;
+    const int H = tower == 0 ? kEvalMotionH : kEvalTextH, M = 16;
+    const std::string p = tower == 0 ? "t2m_motionencoder" : "t2m_textencoder";
+    std::vector<float> hx((size_t)M * H);
+    for (auto& v : hx) v = 2.0f * rng.uni() - 1.0f;
+    ProbeDev x, y;
+    if (x.up(hx) || y.make((size_t)M * 3 * H)) return e->fail(MLDHIP_EHIP, "range probe: hipMalloc");
+    for (int dir = 0; dir < 2; ++dir) {
+      const float* W = P(e, p + (dir ? ".gru.weight_hh_l0_reverse" : ".gru.weight_hh_l0"));
+      for (int split = 1; split >= 0; --split) {
+        Ctx c{e, stream};
+        gemm_eval(c, lin_args(x.p, H, H, W, nullptr, y.p, 3 * H, M, 3 * H), split != 0);
+        if (c.rc) return c.rc;
+        if (int rc = probe_down(e, stream, y.p, (size_t)M * 3 * H, split ? ha : hb)) return rc;
+      }
+      worst = std::max(worst, rel_err(ha, hb));
+    }
+  }
+  e->probe_err_eval = worst;
+  e->eval_split_ok = worst < 0.f || worst <= MLDHIP_PROBE_TOL;
+  return MLDHIP_OK;
+}
+
 int range_probe(E* e, hipStream_t stream, const float* user_text, const float* user_lat, int user_B) {
   Scoped<bool> noise_off(e->noise_off, true);      // deterministic on every handle: the probe compares arithmetic on the eta = 0 step (include/mldhip.h "range_probe")
   ProbeRng rng;
@@ -327,6 +400,8 @@ int range_probe(E* e, hipStream_t stream, const float* user_text, const float* u
     if (int rc = probe_novae(e, stream, rng)) return rc;
   if (e->cfg.clip_layers > 0 && e->group_ready[4] && e->arena_x3)
     if (int rc = probe_text(e, stream, rng)) return rc;
+  if (e->cfg.t2m_eval && (e->group_ready[5] || e->group_ready[6]) && e->arena_x3)
+    if (int rc = probe_eval(e, stream, rng)) return rc;
   e->phase = 0;
   return MLDHIP_OK;
 }

@@ -13,7 +13,7 @@ struct Param {
   size_t offset = 0;   // floats into the arena
   size_t numel = 0;
   bool loaded = false;
-  int group = 0;       // 0 denoiser, 1 vae decoder, 2 dataset statistics, 3 vae encoder, 4 CLIP text tower
+  int group = 0;       // 0 denoiser, 1 vae decoder, 2 dataset statistics, 3 vae encoder, 4 CLIP text tower, 5 T2M motion evaluators (+ mean_eval / std_eval), 6 T2M text evaluator
 };
 
 struct EncLayerP {   // TransformerEncoderLayer (cross_attention.py:236-272)
@@ -55,6 +55,7 @@ struct WsContext {
   StartRow* starts = nullptr;          // [max_batch] start entry per motion of the call (mldhip_sample_many_from; uploaded with every such call, like traj: a replay reads fresh caller buffers and first steps)
   std::vector<StartRow> starts_host;   // stable host copy of what is uploaded to `starts`
   std::vector<int32_t> clip_tab_host;  // text tower: stable host copy of the call's row / prompt tables (engine/path_clip.hpp)
+  std::vector<int32_t> eval_tab_host;  // evaluator towers: stable host copy of the call's length tables (engine/path_eval.hpp)
   bool used = false;
   unsigned long long seed_host = 0;   // stable host copy of the Philox seed while it is uploaded to seed_slot
 #if !defined(MLDHIP_SIM)
@@ -75,7 +76,8 @@ struct mldhip_engine {
   int device = 0;
   std::string err;
   bool finalized = false;
-  bool group_ready[5] = {false, false, false, false, false};   // denoiser, vae decoder, mean/std, vae encoder, CLIP text tower (clip_layers > 0)
+  static constexpr int kGroups = 7;
+  bool group_ready[kGroups] = {false, false, false, false, false, false, false};   // denoiser, vae decoder, mean/std, vae encoder, CLIP text tower (clip_layers > 0), T2M motion / text evaluators (t2m_eval = 1)
 
   // ---- parameters
   std::vector<Param> params;
@@ -105,6 +107,8 @@ struct mldhip_engine {
   unsigned* cl_host_status = nullptr;   // pinned host word the cluster kernel sets next to its sticky status word: read at the start of every sample call (no device synchronisation) -- a timed-out handle leaves the cluster loop by itself
   bool cluster_foreign = false;   // another PROCESS holds the cluster lane of this device (lock file taken at mldhip_create): this handle never launches the cluster loop
   int cluster_failed = 0;         // a cluster launch reported a timeout / a placement it cannot use: the handle stays on the other loop families
+  float* eval_tabs = nullptr;     // evaluator towers: tables derived from the weights at finalize (tap-major convolution weights, the text tower's input_emb padded to K = 384, the folded GRU input biases)
+  float *ev_conv1_w = nullptr, *ev_conv2_w = nullptr, *ev_text_in_w = nullptr, *ev_mbias = nullptr, *ev_tbias = nullptr;   // ... views into it
   float* arena_x3 = nullptr;  // split-f16 (hi | lo half) image of the arena (precision modes with split-f16 staged GEMMs; built by finalize)
   size_t arena_floats = 0;
   std::vector<EncLayerP> den;      // execution order
@@ -143,6 +147,9 @@ struct mldhip_engine {
   float *cv1, *cvec, *LNO, *feats_int, *joints_int, *zbuf;
   // CLIP text tower (clip_layers > 0; engine/path_clip.hpp): packed token rows [clip_max_prompts x clip_ctx][..], EOS rows / embeddings [clip_max_prompts][text_dim], int tables
   float *cX = nullptr, *cLN = nullptr, *cQKV = nullptr, *cAO = nullptr, *cFF = nullptr, *cE0 = nullptr, *cE1 = nullptr, *cTab = nullptr;
+  // T2M evaluator towers (t2m_eval = 1; engine/path_eval.hpp), sized for one chunk of kEvalChunk motions: convolution staging G0 / G1, row buffers A / B (512 .. 1024 wide),
+  // the input-side gate products Gi [rows][6H], the double-buffered state h0 / h1 [motions][2H], the head's rows, int tables
+  float *vG0 = nullptr, *vG1 = nullptr, *vA = nullptr, *vB = nullptr, *vGi = nullptr, *vH0 = nullptr, *vH1 = nullptr, *vHead = nullptr, *vTab = nullptr;
   float* len_rep = nullptr;   // [max_batch] ints: first sample of each sample's length (length_reps_kernel; decoder layer 0 under "dec_lean")
   float* FS = nullptr;   // sample-major loop: parked skip activations [ceil(max_batch / 8)][nb][48][256]
   float *cl_xbuf = nullptr, *cl_park = nullptr, *cl_flags = nullptr;   // cluster loop: exchange regions [clusters][kClXFloats], parked skip rows [workgroups][nb][16][256], flags [clusters][64] + status [16] (words)
@@ -194,6 +201,8 @@ struct mldhip_engine {
   float probe_err_decode_half = -1.f;
   bool text_split_ok = true;     // false: the CLIP text tower (engine/path_clip.hpp) runs its GEMMs and attention on exact-fp32 MFMAs
   float probe_err_text = -1.f;   // the tower stage's reading (-1: not probed / no tower)
+  bool eval_split_ok = true;     // false: the T2M evaluator towers (engine/path_eval.hpp) run their GEMMs and the recurrence on exact-fp32 MFMAs
+  float probe_err_eval = -1.f;   // the evaluator stage's reading (-1: not probed / no evaluators)
   float probe_err_loop = -1.f, probe_err_decode = -1.f;   // probe results (max-abs difference / max-abs reference); -1: not probed
   unsigned* nonfinite = nullptr; // device counter: non-finite values seen in the latents / joints a sample call produced (sticky until read)
 
@@ -212,7 +221,7 @@ struct mldhip_engine {
   // every device allocation the handle owns outside its contexts: teardown frees what is listed HERE (a new buffer is added beside its declaration, nowhere else)
   std::vector<void**> device_buffers() {
     return {(void**)&arena, (void**)&arena_x3, (void**)&ffn_streams, (void**)&loop_stream, (void**)&loop_stream_x3, (void**)&cl_stream,
-            (void**)&cl_wave_off_dev, (void**)&loop_small, (void**)&trace_buf, (void**)&nonfinite};
+            (void**)&cl_wave_off_dev, (void**)&loop_small, (void**)&trace_buf, (void**)&nonfinite, (void**)&eval_tabs};
   }
 
   int fail(int code, const char* fmt, ...) {

@@ -21,7 +21,7 @@
 
 namespace mld {
 
-enum Act : int { ACT_NONE = 0, ACT_GELU = 1, ACT_SILU = 2, ACT_QGELU = 3 };   // ACT_QGELU: x * sigmoid(1.702 x), CLIP's quick_gelu (EPI = 1 instantiations only)
+enum Act : int { ACT_NONE = 0, ACT_GELU = 1, ACT_SILU = 2, ACT_QGELU = 3, ACT_LRELU = 4 };   // ACT_QGELU: x * sigmoid(1.702 x), CLIP's quick_gelu (EPI = 1 instantiations only); ACT_LRELU: LeakyReLU(0.2) (EPI = 2 only)
 
 struct GemmArgs {
   const float* A = nullptr;  int lda = 0;  int K1 = 0;   // first K segment  [M, K1]
@@ -130,7 +130,9 @@ constexpr int gemm_lds_bytes() {    // the chunk double buffer, or the output ti
 //                 runtime branch around a prefetch load makes hipcc's vmcnt bookkeeping conservative and the
 //                 ring drains at every LDS store (seen in the ISA as vmcnt(5)..vmcnt(0) ladders).
 // EPI (staged, !LN): 0 = the epilogues above; 1 = the CLIP text tower's (kernels/clip_text.hpp): bias, then quick-GELU (act == ACT_QGELU) or a
-//                 plain residual add (res / ldres, no LayerNorm behind it; Y may be res: every element is read and written by one thread).
+//                 plain residual add (res / ldres, no LayerNorm behind it; Y may be res: every element is read and written by one thread);
+//                 2 = the T2M evaluator towers' (engine/path_eval.hpp): bias, then LeakyReLU(0.2) (act == ACT_LRELU) or nothing; rows masked by lens /
+//                 rows_per_group are stored as zeros by SELECTION (not by a product: such a row may hold anything, it is a convolution's padding row).
 template <int WM, int WN, int MREP, int NREP, bool LN, bool STAGED = false, int PREC = 0, int KCS = 0, bool TRACE = false, int EPI = 0>
 __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs p) {
   static_assert(PREC == PREC_F32 || STAGED, "reduced-precision operands need the LDS-staged main loop");
@@ -178,7 +180,19 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs p) {
     else load_frags<MREP>(fa, p.A2, p.lda2, m0, p.M, k - p.K1, r, g, relu);
     load_frags<NREP>(fb, W, p.ldw, n0, p.N, k, r, g, false);
   };
-  auto compute = [&](Frag(&fa)[MREP], Frag(&fb)[NREP]) {
+  // EPI = 2 (the evaluator towers: K up to 2 048, results held to a few float32-CPU errors of float64): the four chunks of a pipeline round accumulate into four
+  // accumulator sets that meet pairwise behind the main loop -- four k-ordered chains of K / 4 instead of one of K.  Every other instantiation has the one set `acc`.
+  constexpr int NXS = EPI == 2 ? 3 : 1;
+  f32x4 accx[NXS][MREP][NREP];
+  if constexpr (EPI == 2) {
+#pragma unroll
+    for (int x = 0; x < NXS; ++x)
+#pragma unroll
+      for (int a = 0; a < MREP; ++a)
+#pragma unroll
+        for (int b = 0; b < NREP; ++b) accx[x][a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  auto compute = [&](Frag(&fa)[MREP], Frag(&fb)[NREP], f32x4 (&dst)[MREP][NREP]) {
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
@@ -186,7 +200,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs p) {
 #pragma unroll
         for (int b = 0; b < NREP; ++b) {
           if (SPLIT && (i & 1)) acc2 = mfma_f32_16x16x4(fa[a].v[i], fb[b].v[i], acc2);
-          else acc[a][b] = mfma_f32_16x16x4(fa[a].v[i], fb[b].v[i], acc[a][b]);
+          else dst[a][b] = mfma_f32_16x16x4(fa[a].v[i], fb[b].v[i], dst[a][b]);
         }
   };
 
@@ -194,10 +208,10 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs p) {
     load(fa0, fb0, 0);
     for (int kc = 0; kc < KC; kc += 2) {
       if (kc + 1 < KC) load(fa1, fb1, kc + 1);
-      compute(fa0, fb0);
+      compute(fa0, fb0, acc);
       if (kc + 1 < KC) {
         if (kc + 2 < KC) load(fa0, fb0, kc + 2);
-        compute(fa1, fb1);
+        compute(fa1, fb1, acc);
       }
     }
   } else {
@@ -306,7 +320,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs p) {
         blo[t] = rp[4 + g];
       }
     };
-    auto mma_narrow = [&](int buf) {       // PREC_BF16: one matrix instruction per tile and K chunk
+    auto mma_narrow = [&](int buf, f32x4 (&dst)[MREP][NREP]) {       // PREC_BF16: one matrix instruction per tile and K chunk
       const float* as = smem + buf * ROWS * kGemmLdsStride + (wm * MREP * 16 + r) * kGemmLdsStride;
       const float* ws = smem + buf * ROWS * kGemmLdsStride + (BM + wn * NREP * 16 + r) * kGemmLdsStride;
 #pragma unroll
@@ -316,27 +330,27 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs p) {
 #pragma unroll
       for (int a = 0; a < MREP; ++a)
 #pragma unroll
-        for (int b = 0; b < NREP; ++b) acc[a][b] = mfma_bf16_16x16x32(ahi[a], bhi[b], acc[a][b]);
+        for (int b = 0; b < NREP; ++b) dst[a][b] = mfma_bf16_16x16x32(ahi[a], bhi[b], dst[a][b]);
     };
-    auto compute_bf16 = [&]() {
+    auto compute_bf16 = [&](f32x4 (&dst)[MREP][NREP]) {
 #pragma unroll
       for (int a = 0; a < MREP; ++a)
 #pragma unroll
         for (int b = 0; b < NREP; ++b) {
-          acc[a][b] = mfma_x3_16x16x32(alo[a], bhi[b], acc[a][b]);
-          acc[a][b] = mfma_x3_16x16x32(ahi[a], blo[b], acc[a][b]);
-          acc[a][b] = mfma_x3_16x16x32(ahi[a], bhi[b], acc[a][b]);
+          dst[a][b] = mfma_x3_16x16x32(alo[a], bhi[b], dst[a][b]);
+          dst[a][b] = mfma_x3_16x16x32(ahi[a], blo[b], dst[a][b]);
+          dst[a][b] = mfma_x3_16x16x32(ahi[a], bhi[b], dst[a][b]);
         }
     };
-    auto mma = [&](int buf) {
+    auto mma = [&](int buf, f32x4 (&dst)[MREP][NREP]) {
       if constexpr (PREC == PREC_F32) {
         lfrags(buf);
-        compute(fa0, fb0);
+        compute(fa0, fb0, dst);
       } else if constexpr (PREC == PREC_F16X3) {
         lfrags_bf16(buf);
-        compute_bf16();
+        compute_bf16(dst);
       } else {
-        mma_narrow(buf);
+        mma_narrow(buf, dst);
       }
     };
     static_assert(KCS >= 4 && KCS % 4 == 0, "staged GEMMs take K in {256, 512, 1024}");
@@ -351,19 +365,19 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs p) {
 #pragma unroll
     for (int kc = 0; kc < KCS; kc += 4) {
       if constexpr (TRACE) { if (kc == 4) ts[2] = clock_pinned(); }   // 4 chunks done
-      mma(0);                                                       // chunk kc   (buffer 0)
+      mma(0, acc);                                                  // chunk kc   (buffer 0)
       lstore(1, st1);
       if (kc + 5 < KCS) gload(st1, kc + 5);                         // kc is a constant after unrolling
       __syncthreads();
-      mma(1);                                                       // chunk kc+1 (buffer 1)
+      if constexpr (EPI == 2) mma(1, accx[0]); else mma(1, acc);    // chunk kc+1 (buffer 1)
       lstore(0, st2);
       if (kc + 6 < KCS) gload(st2, kc + 6);
       __syncthreads();
-      mma(0);                                                       // chunk kc+2
+      if constexpr (EPI == 2) mma(0, accx[1]); else mma(0, acc);    // chunk kc+2
       lstore(1, st3);
       if (kc + 7 < KCS) gload(st3, kc + 7);
       __syncthreads();
-      mma(1);                                                       // chunk kc+3
+      if constexpr (EPI == 2) mma(1, accx[2]); else mma(1, acc);    // chunk kc+3
       if (kc + 4 < KCS) {
         lstore(0, st0);
         if (kc + 8 < KCS) gload(st0, kc + 8);
@@ -372,6 +386,12 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs p) {
     }
   }
   if (SPLIT) acc[0][0] += acc2;
+  if constexpr (EPI == 2) {
+#pragma unroll
+    for (int a = 0; a < MREP; ++a)
+#pragma unroll
+      for (int b = 0; b < NREP; ++b) acc[a][b] = (acc[a][b] + accx[0][a][b]) + (accx[1][a][b] + accx[2][a][b]);
+  }
   if constexpr (TRACE) ts[3] = clock_pinned();              // main loop done
   auto trace_out = [&]() {
     if constexpr (TRACE) {
@@ -453,6 +473,24 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs p) {
           }
       }
     };
+    if constexpr (EPI == 2) {
+      static_assert(STAGED, "the evaluator towers run on the staged tile");
+      auto finish_sel = [&](auto actfn) {
+#pragma unroll
+        for (int b = 0; b < NREP; ++b)
+#pragma unroll
+          for (int a = 0; a < MREP; ++a)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+              Cs[(wm * MREP * 16 + a * 16 + g * 4 + i) * (BN + 4) + wn * NREP * 16 + b * 16 + r] = rowmask[a][i] != 0.f ? actfn(acc[a][b][i] + bv[b]) : 0.f;
+      };
+      if (p.act == ACT_LRELU) finish_sel([](float x) { return x > 0.f ? x : 0.2f * x; });
+      else finish_sel([](float x) { return x; });
+      __syncthreads();
+      store_tile_from_lds<BM, BN, WM * WN * 64>(Cs, Y, p.ldy, blockIdx.x * BM, blockIdx.y * BN, p.M, p.N, tid);
+      trace_out();
+      return;
+    }
     if constexpr (EPI == 1) {
       static_assert(STAGED, "the residual epilogue adds while the parked tile is stored");
       if (p.act == ACT_QGELU) finish([](float x) { return quick_gelu(x); });

@@ -12,7 +12,7 @@
 //
 // Source layout: engine/state.hpp (handle, contexts) -> engine/params.hpp (weight contract, schedules) ->
 // engine/dispatch.hpp (kernel selection, the counted launch) -> engine/path_loop.hpp (the latent models' reverse loop) -> engine/streams.hpp (finalize-time weight
-// images) -> engine/path_vae.hpp (VAE decode / encode, feats2joints) -> engine/path_latent.hpp / engine/path_novae.hpp / engine/path_clip.hpp (the sample calls, the text tower) ->
+// images) -> engine/path_vae.hpp (VAE decode / encode, feats2joints) -> engine/path_latent.hpp / engine/path_novae.hpp / engine/path_clip.hpp / engine/path_eval.hpp (the sample calls, the text tower, the T2M evaluator towers) ->
 // engine/graphs.hpp (graph capture and caches) -> engine/create.hpp (validation, workspace carve, LDS registration, teardown) ->
 // engine/serve.hpp (the sampling drivers and their shared host sequences) -> engine/probe.hpp (range probe) -> the C ABI below: each
 // entry point is its argument checks and a call into the engine.  kernels/*.hpp hold the device code (no __global__ in this file).
@@ -51,6 +51,7 @@
 #include "kernels/final_strip.hpp"
 #include "kernels/dec_half.hpp"
 #include "kernels/clip_text.hpp"
+#include "kernels/gru.hpp"
 
 using namespace mld;
 
@@ -63,6 +64,7 @@ using namespace mld;
 #include "engine/path_latent.hpp"
 #include "engine/path_novae.hpp"
 #include "engine/path_clip.hpp"
+#include "engine/path_eval.hpp"
 #include "engine/graphs.hpp"
 #include "engine/create.hpp"
 #include "engine/serve.hpp"
@@ -89,6 +91,8 @@ void mldhip_default_config(mldhip_config* c) {
   c->max_in_flight = 1;
   // no text tower by default (clip_layers 0); the other fields are CLIP ViT-L/14's, clip_max_prompts 0 = 2 x max_batch
   c->clip_layers = 0; c->clip_heads = 12; c->clip_ff = 3072; c->clip_vocab = 49408; c->clip_ctx = 77; c->clip_max_prompts = 0;
+  // no T2M evaluator towers by default (t2m_eval 0); t2m_max_motions 0 = 2 x max_batch, t2m_max_words 0 = 32
+  c->t2m_eval = 0; c->t2m_max_motions = 0; c->t2m_max_words = 0;
 }
 
 const char* mldhip_last_error(mldhip_handle* h) { return h ? h->err.c_str() : g_last_error.c_str(); }
@@ -98,14 +102,17 @@ int mldhip_create(const mldhip_config* cfg, int device, mldhip_handle** out) {
   if (!cfg || !out) return bad("null argument");
   // ABI 6 appended `eta`: a caller built against ABI 5 passes the smaller struct (eta is 0 then); the fields are read from a full-size copy
   // ABI 7 appended the clip_* fields: a caller built against ABI 6 passes the struct that ends behind eta (no text tower then)
-  constexpr int32_t kCfgAbi5 = (int32_t)offsetof(mldhip_config, eta), kCfgAbi6 = (int32_t)offsetof(mldhip_config, clip_layers);
-  if (cfg->struct_size != (int32_t)sizeof(mldhip_config) && cfg->struct_size != kCfgAbi5 && cfg->struct_size != kCfgAbi6) return bad("mldhip_config.struct_size mismatch (ABI skew)");
+  // the t2m_* fields came behind the clip_* fields without a new ABI number: a caller built before them passes the struct that ends behind clip_max_prompts (no evaluators then)
+  constexpr int32_t kCfgAbi5 = (int32_t)offsetof(mldhip_config, eta), kCfgAbi6 = (int32_t)offsetof(mldhip_config, clip_layers), kCfgNoEval = (int32_t)offsetof(mldhip_config, t2m_eval);
+  if (cfg->struct_size != (int32_t)sizeof(mldhip_config) && cfg->struct_size != kCfgAbi5 && cfg->struct_size != kCfgAbi6 && cfg->struct_size != kCfgNoEval) return bad("mldhip_config.struct_size mismatch (ABI skew)");
   mldhip_config full;
   mldhip_default_config(&full);                       // fields the caller's struct does not cover keep their defaults ...
   if (cfg->struct_size == kCfgAbi5) full.eta = 0.0f;
   std::memcpy(&full, cfg, (size_t)cfg->struct_size);  // ... every field it covers is the caller's
   full.struct_size = (int32_t)sizeof(mldhip_config);
   if (full.clip_layers > 0 && full.clip_max_prompts == 0) full.clip_max_prompts = 2 * full.max_batch;
+  if (full.t2m_eval && full.t2m_max_motions == 0) full.t2m_max_motions = 2 * full.max_batch;
+  if (full.t2m_eval && full.t2m_max_words == 0) full.t2m_max_words = 32;
   if (const char* what = config_error(&full)) return bad(what);
   int num_cus = 0;
   if (int rc = check_device(device, &num_cus)) return rc;
@@ -269,12 +276,13 @@ int mldhip_finalize_weights(mldhip_handle* e, void* stream_) {
   DeviceGuard dg(e->device);
   // A group (denoiser / vae decoder / mean+std) must be loaded completely or not at all; ops of an
   // absent group fail with MLDHIP_ESTATE, sample() needs all three.
-  int have[5] = {0, 0, 0, 0, 0}, total[5] = {0, 0, 0, 0, 0};
-  for (auto& p : e->params) { total[p.group]++; have[p.group] += p.loaded; }
+  constexpr int NG = mldhip_engine::kGroups;
+  int have[NG] = {0}, total[NG] = {0}, any = 0;
+  for (auto& p : e->params) { total[p.group]++; have[p.group] += p.loaded; any += p.loaded; }
   for (auto& p : e->params)
     if (!p.loaded && have[p.group] != 0) return e->fail(MLDHIP_ENOKEY, "missing tensor %s (strict load)", p.key.c_str());
-  if (have[0] + have[1] + have[2] + have[3] + have[4] == 0) return e->fail(MLDHIP_ENOKEY, "no tensors loaded");
-  for (int g = 0; g < 5; ++g) e->group_ready[g] = total[g] > 0 && have[g] == total[g];
+  if (any == 0) return e->fail(MLDHIP_ENOKEY, "no tensors loaded");
+  for (int g = 0; g < NG; ++g) e->group_ready[g] = total[g] > 0 && have[g] == total[g];
   hipStream_t stream = (hipStream_t)stream_;
   bind_layers(e);
   Ctx c{e, stream};
@@ -290,6 +298,7 @@ int mldhip_finalize_weights(mldhip_handle* e, void* stream_) {
   if (int rc = build_loop_stream(c)) return rc;
   if (int rc = build_cluster_stream(c)) return rc;
   if (int rc = build_ffn_streams(c)) return rc;
+  if (int rc = build_eval_tables(c)) return rc;
   for (int k = 0; k < (int)e->ctxs.size(); ++k) {       // the derived tables live in each context's workspace
   bind_context(e, k);
   if (e->group_ready[0]) {
@@ -332,8 +341,8 @@ int mldhip_finalize_weights(mldhip_handle* e, void* stream_) {
   if (e->loop_kernel == 3 && !e->loop_ips)      // (set before finalize: refused here, like mldhip_set_option refuses it afterwards)
     return e->fail(MLDHIP_EINVAL, "loop_kernel 3: the sample-major loop is built for fp32 / split-f16 loop arithmetic, latent_dim 256, ff_size 1024, 4 heads");
   e->finalized = true;
-  e->split_loop_ok = e->split_decode_ok = e->dec_half_ok = e->text_split_ok = true;
-  e->probe_err_loop = e->probe_err_decode = e->probe_err_decode_half = e->probe_err_text = -1.f;
+  e->split_loop_ok = e->split_decode_ok = e->dec_half_ok = e->text_split_ok = e->eval_split_ok = true;
+  e->probe_err_loop = e->probe_err_decode = e->probe_err_decode_half = e->probe_err_text = e->probe_err_eval = -1.f;
   if (e->cfg.precision == MLDHIP_PREC_F16X3 && e->range_probe) {
     if (int rc = range_probe(e, stream)) { e->finalized = false; return rc; }
     e->probe_first_call = e->range_probe == 2;
@@ -344,8 +353,9 @@ int mldhip_finalize_weights(mldhip_handle* e, void* stream_) {
 int mldhip_numeric_status(mldhip_handle* e, mldhip_numeric_info* out) {
   if (!e || !out) return MLDHIP_EINVAL;
   // ABI 8 appended the text tower's two fields: a caller built against ABI 7 passes the struct that ends behind `reserved` and gets the fields it knows
-  constexpr int32_t kInfoAbi7 = (int32_t)offsetof(mldhip_numeric_info, text_split_ok);
-  if (out->struct_size != (int32_t)sizeof(mldhip_numeric_info) && out->struct_size != kInfoAbi7) return e->fail(MLDHIP_EINVAL, "mldhip_numeric_info.struct_size mismatch (ABI)");
+  // ... and the evaluator towers' two fields came behind them: the struct that ends behind probe_err_text is accepted too
+  constexpr int32_t kInfoAbi7 = (int32_t)offsetof(mldhip_numeric_info, text_split_ok), kInfoNoEval = (int32_t)offsetof(mldhip_numeric_info, eval_split_ok);
+  if (out->struct_size != (int32_t)sizeof(mldhip_numeric_info) && out->struct_size != kInfoAbi7 && out->struct_size != kInfoNoEval) return e->fail(MLDHIP_EINVAL, "mldhip_numeric_info.struct_size mismatch (ABI)");
   DeviceGuard dg(e->device);
   HIP_TRY(e, hipDeviceSynchronize());
   unsigned n = 0;
@@ -354,7 +364,7 @@ int mldhip_numeric_status(mldhip_handle* e, mldhip_numeric_info* out) {
   // a cluster launch that ran into its wait bound poisoned its latents (counted above) and left its status word set: the handle stays off the cluster loop from here on
   // (the captured graphs that hold it are dropped); mldhip_set_option("loop_kernel", 4) re-arms it
   if (!e->cluster_failed && cluster_timed_out(e)) leave_cluster_loop(e);
-  out->probed = e->probe_err_loop >= 0.f || e->probe_err_decode >= 0.f || e->probe_err_text >= 0.f;
+  out->probed = e->probe_err_loop >= 0.f || e->probe_err_decode >= 0.f || e->probe_err_text >= 0.f || e->probe_err_eval >= 0.f;
   out->loop_split_ok = e->cfg.precision == MLDHIP_PREC_F16X3 && e->split_loop_ok;
   out->decode_split_ok = e->cfg.precision == MLDHIP_PREC_F16X3 && e->split_decode_ok;
   out->probe_err_loop = e->probe_err_loop;
@@ -367,6 +377,10 @@ int mldhip_numeric_status(mldhip_handle* e, mldhip_numeric_info* out) {
   if (out->struct_size > kInfoAbi7) {
     out->text_split_ok = e->cfg.clip_layers > 0 && e->cfg.precision == MLDHIP_PREC_F16X3 && e->arena_x3 && e->text_split_ok;
     out->probe_err_text = e->probe_err_text;
+  }
+  if (out->struct_size > kInfoNoEval) {
+    out->eval_split_ok = e->cfg.t2m_eval && e->cfg.precision == MLDHIP_PREC_F16X3 && e->arena_x3 && e->eval_split_ok;
+    out->probe_err_eval = e->probe_err_eval;
   }
   return MLDHIP_OK;
 }
@@ -598,6 +612,19 @@ int mldhip_text_encode(mldhip_handle* e, const int32_t* ids_host, const int32_t*
   if (!e) return MLDHIP_EINVAL;
   DeviceGuard dg(e->device);
   return text_encode_impl(e, ids_host, eos_pos_host, P, text_emb_out_dev, (hipStream_t)stream_);
+}
+
+int mldhip_t2m_motion_embed(mldhip_handle* e, const float* feats_dev, const int32_t* lengths_host, int32_t B, int32_t T, int32_t renorm, float* emb_out_dev, void* stream_) {
+  if (!e) return MLDHIP_EINVAL;
+  DeviceGuard dg(e->device);
+  return t2m_motion_embed_impl(e, feats_dev, lengths_host, B, T, renorm, emb_out_dev, (hipStream_t)stream_);
+}
+
+int mldhip_t2m_text_embed(mldhip_handle* e, const float* word_embs_dev, const float* pos_ohot_dev, const int32_t* text_lengths_host, int32_t B, int32_t L,
+                          float* emb_out_dev, void* stream_) {
+  if (!e) return MLDHIP_EINVAL;
+  DeviceGuard dg(e->device);
+  return t2m_text_embed_impl(e, word_embs_dev, pos_ohot_dev, text_lengths_host, B, L, emb_out_dev, (hipStream_t)stream_);
 }
 
 int mldhip_feats2joints(mldhip_handle* e, const float* feats_dev, int32_t B, int32_t T, float* joints_out_dev, void* stream_) {

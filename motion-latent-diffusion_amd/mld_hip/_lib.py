@@ -37,6 +37,7 @@ class Config(C.Structure):
         ("eta", C.c_float),
         ("clip_layers", C.c_int32), ("clip_heads", C.c_int32), ("clip_ff", C.c_int32), ("clip_vocab", C.c_int32),
         ("clip_ctx", C.c_int32), ("clip_max_prompts", C.c_int32),
+        ("t2m_eval", C.c_int32), ("t2m_max_motions", C.c_int32), ("t2m_max_words", C.c_int32),
     ]
 
 
@@ -62,7 +63,7 @@ class NumericInfo(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("probed", C.c_int32), ("loop_split_ok", C.c_int32), ("decode_split_ok", C.c_int32),
                 ("probe_err_loop", C.c_float), ("probe_err_decode", C.c_float), ("nonfinite_values", C.c_int64),
                 ("decode_half_ok", C.c_int32), ("probe_err_decode_half", C.c_float), ("cluster_loop", C.c_int32), ("reserved", C.c_int32),
-                ("text_split_ok", C.c_int32), ("probe_err_text", C.c_float)]
+                ("text_split_ok", C.c_int32), ("probe_err_text", C.c_float), ("eval_split_ok", C.c_int32), ("probe_err_eval", C.c_float)]
 
 
 PROBE_TOL = 6e-6                         # MLDHIP_PROBE_TOL
@@ -110,6 +111,8 @@ _SYMBOLS = {
     "mldhip_ddim_step_eta": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p,
                                        C.c_int64, C.c_void_p]),
     "mldhip_text_encode": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_void_p]),
+    "mldhip_t2m_motion_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mldhip_t2m_text_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "mldhip_feats2joints": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "mldhip_get_timesteps": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]),
     "mldhip_get_alphas_cumprod": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int32]),
@@ -378,6 +381,18 @@ class Engine:
             raise ValueError(f"ids must be [P, {self.cfg.clip_ctx}] with one eos_pos per row, got {ids.shape} / {eos.shape}")
         self._check(self.lib.mldhip_text_encode(self._h, ids.ctypes.data_as(C.POINTER(C.c_int32)), eos.ctypes.data_as(C.POINTER(C.c_int32)),
                                                 int(ids.shape[0]), _ptr(out), stream))
+
+    def t2m_motion_embed(self, feats, lengths: Sequence[int], T: int, out, renorm: bool = True, stream: int = 0):
+        """The T2M motion evaluator tower (mldhip_t2m_motion_embed; engines created with t2m_eval=1): ``feats`` [B, T, nfeats] on the device, ``lengths`` [B]
+        on the host (each 4 .. T), ``out`` [B, 512] on the device.  ``renorm``: apply renorm4t2m first (needs mean / std and mean_eval / std_eval)."""
+        lens = (C.c_int32 * len(lengths))(*[int(x) for x in lengths])
+        self._check(self.lib.mldhip_t2m_motion_embed(self._h, _ptr(feats), lens, len(lengths), int(T), 1 if renorm else 0, _ptr(out), stream))
+
+    def t2m_text_embed(self, word_embs, pos_ohot, text_lengths: Sequence[int], L: int, out, stream: int = 0):
+        """The T2M text evaluator tower (mldhip_t2m_text_embed): ``word_embs`` [B, L, 300] and ``pos_ohot`` [B, L, 15] on the device, ``text_lengths`` [B] on the
+        host (each 1 .. L), ``out`` [B, 512] on the device."""
+        lens = (C.c_int32 * len(text_lengths))(*[int(x) for x in text_lengths])
+        self._check(self.lib.mldhip_t2m_text_embed(self._h, _ptr(word_embs), _ptr(pos_ohot), lens, len(text_lengths), int(L), _ptr(out), stream))
 
     def feats2joints(self, feats, B: int, T: int, joints_out, stream: int = 0):
         self._check(self.lib.mldhip_feats2joints(self._h, _ptr(feats), B, T, _ptr(joints_out), stream))

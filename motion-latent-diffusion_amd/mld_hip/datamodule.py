@@ -31,7 +31,7 @@ class HipDataModule:
 
     def __init__(self, cfg=None, mean: Optional[np.ndarray] = None, std: Optional[np.ndarray] = None,
                  nfeats: Optional[int] = None, njoints: Optional[int] = None, engine_key: Optional[str] = None, name: Optional[str] = None,
-                 nclasses: int = 12, variant: Optional[str] = None):
+                 nclasses: int = 12, variant: Optional[str] = None, mean_eval: Optional[np.ndarray] = None, std_eval: Optional[np.ndarray] = None):
         """name 'humanml3d' (263-d features, 22 joints), 'kit' (KIT-ML: 251-d features, 21 joints; mld/data/Kit.py) or 'humanact12' (rot6d 25x6 =
         150-d features, 12 classes; mld/data/HumanAct12.py) -- the last only carries shapes: its feats2joints needs SMPL.  What is not passed comes
         from `cfg`: the name from TEST.DATASETS[0] (how the reference's get_data.py picks the datamodule), the widths from DATASET.NFEATS / NJOINTS
@@ -60,7 +60,16 @@ class HipDataModule:
                 self.stats = "synthetic"
         self.mean = np.asarray(mean, np.float32)
         self.std = np.asarray(std, np.float32)
-        self.hparams = type("H", (), {"mean": self.mean, "std": self.std})()
+        # the T2M evaluators' own statistics (get_data.py:86: get_mean_std("val", ...)): mean_eval.npy / std_eval.npy beside Mean.npy where they exist, synthetic otherwise
+        if mean_eval is None or std_eval is None:
+            root = _from_cfg(cfg, "DATASET", layout[2], "ROOT")
+            if root and os.path.exists(os.path.join(root, "mean_eval.npy")) and os.path.exists(os.path.join(root, "std_eval.npy")):
+                mean_eval, std_eval = np.load(os.path.join(root, "mean_eval.npy")), np.load(os.path.join(root, "std_eval.npy"))
+            else:
+                mean_eval, std_eval = syn.make_mean_std_eval(nfeats)
+        self.mean_eval = np.asarray(mean_eval, np.float32)
+        self.std_eval = np.asarray(std_eval, np.float32)
+        self.hparams = type("H", (), {"mean": self.mean, "std": self.std, "mean_eval": self.mean_eval, "std_eval": self.std_eval})()
         self._engine_key = engine_key
         self._shared_arch = {}          # architecture fields of the model this datamodule serves (set by MLD)
         self._loaded_on = None
@@ -76,6 +85,12 @@ class HipDataModule:
             self._loaded_on = eng
             owners["mean/std"] = id(self)
         return eng
+
+    def renorm4t2m(self, features: torch.Tensor) -> torch.Tensor:
+        """HumanML3D.py:54-63 / Kit.py:49-58: the model's normalisation -> the T2M evaluators', on every frame (padded ones included)"""
+        mean, std = torch.from_numpy(self.mean).to(features), torch.from_numpy(self.std).to(features)
+        mean_eval, std_eval = torch.from_numpy(self.mean_eval).to(features), torch.from_numpy(self.std_eval).to(features)
+        return (features * std + mean - mean_eval) / std_eval
 
     def feats2joints(self, features: torch.Tensor, mask=None) -> torch.Tensor:
         """[B, T, nfeats] -> [B, T, njoints, 3] (HumanML3D.py:41-45 / Kit.py: recover_from_ric with the datamodule's njoints), on the tensor's device."""

@@ -57,14 +57,17 @@ class MLD(nn.Module):
         self.vae = instantiate_from_config(cfg.model.motion_vae) if self.vae_type != "no" else None      # mld.py:58-59
         self.denoiser = instantiate_from_config(cfg.model.denoiser)
         self.scheduler = instantiate_from_config(cfg.model.scheduler)
-        for m in (self.vae, self.denoiser, self.text_encoder):
+        # the T2M evaluator nets (mld.py:110-140) are opt-in: cfg.model.t2m_evaluator.target = mld_hip.evaluators.HipT2MEvaluator; without it t2m_* keys are dropped
+        ev = cfg.model.get("t2m_evaluator") if hasattr(cfg.model, "get") else None
+        self.t2m_evaluator = instantiate_from_config(ev) if ev and ev.get("target") else None
+        for m in (self.vae, self.denoiser, self.text_encoder, self.t2m_evaluator):
             if engine_key is not None and m is not None and hasattr(m, "use_engine"):
                 m.use_engine(engine_key)
         # ONE engine for all parts of this model: every part asks the registry for the union of the architecture fields
         # (the fused sample() needs every weight group in one handle); another model with other fields gets its own engine
         shared = {}
         # (the datamodule first: its skeleton -- njoints, the feature width -- then the networks'; a HipMldTextEncoder adds the tower's fields: its weights live in the same handle)
-        for m in (datamodule, self.denoiser, self.vae, self.text_encoder):
+        for m in (datamodule, self.denoiser, self.vae, self.text_encoder, self.t2m_evaluator):
             shared.update(getattr(m, "_arch", {}) or {})
         if hasattr(self.scheduler, "engine_config"):
             shared.update(self.scheduler.engine_config(cfg.model.scheduler.num_inference_timesteps))
@@ -76,13 +79,17 @@ class MLD(nn.Module):
             self.eta = 0.0
         if self.vae_type != "no":
             shared["eta"] = self.eta
-        for m in (self.denoiser, self.vae, datamodule, self.scheduler, self.text_encoder):
+        for m in (self.denoiser, self.vae, datamodule, self.scheduler, self.text_encoder, self.t2m_evaluator):
             if m is not None and hasattr(m, "_shared_arch") and engine_key is None:
                 m._shared_arch = shared
         if hasattr(self.text_encoder, "_shared_arch"):
             self.text_encoder._variant = self.variant
         if hasattr(self.scheduler, "_variant"):
             self.scheduler._variant = self.variant
+        if self.t2m_evaluator is not None:
+            self.t2m_evaluator._variant = self.variant
+            if hasattr(datamodule, "mean_eval"):
+                self.t2m_evaluator.stats_eval = (datamodule.mean_eval, datamodule.std_eval)
         self.sample_mean = False
         self.fact = None
         self.do_classifier_free_guidance = self.guidance_scale > 1.0
@@ -94,7 +101,10 @@ class MLD(nn.Module):
         te = self.text_encoder.state_dict() if self.text_encoder is not None else {}
         new = OrderedDict(("text_encoder." + k, v) for k, v in te.items())
         for k, v in state_dict.items():
-            if "text_encoder" not in k and not k.startswith("t2m_"):      # evaluator nets are not part of sampling
+            if k.startswith("t2m_"):      # evaluator nets: loaded (strictly) when the model carries a HipT2MEvaluator, dropped otherwise -- they are not part of sampling
+                if self.t2m_evaluator is not None:
+                    new["t2m_evaluator." + k] = v
+            elif "text_encoder" not in k:
                 new[k] = v
         return super().load_state_dict(new, strict)
 
@@ -111,6 +121,8 @@ class MLD(nn.Module):
         eng = self.denoiser.sync_weights()
         if self.vae is not None:
             self.vae.sync_weights()
+        if self.t2m_evaluator is not None:
+            self.t2m_evaluator.sync_weights()
         want = self.scheduler.engine_config(self.cfg.model.scheduler.num_inference_timesteps)
         for k in ("num_train_timesteps", "num_inference_steps", "steps_offset", "set_alpha_to_one"):
             if getattr(eng.cfg, k) != want[k]:
@@ -353,6 +365,44 @@ class MLD(nn.Module):
             z = self._diffusion_reverse(cond.reshape(-1, 1), lengths, init_latents)
             feats = self.vae.decode(z.contiguous(), lengths)
         return {"m_action": actions, "m_rst": feats, "m_lens": lengths}
+
+    @torch.no_grad()
+    def t2m_eval(self, batch, init_latents: Optional[torch.Tensor] = None, seed: Optional[int] = None):
+        """MLD.t2m_eval for the diffusion stages (mld.py:618-708): batch {"text", "motion" [B, T, nfeats], "length", "word_embs" [B, L, 300], "pos_ohot" [B, L, 15],
+        "text_len"} -> rs_set {"m_ref", "m_rst", "lat_t", "lat_m", "lat_rm"} in the reference's align_idx order (lengths descending) and {"joints_ref", "joints_rst"} in
+        the batch's order, as there.  Generated and ground-truth motions go through ONE mldhip_t2m_motion_embed call of 2B rows (two when their frame counts differ:
+        an embedding depends on T).  Repeating prompts for the multimodality pass (MM_NUM_REPEATS) is the caller's loop."""
+        if self.t2m_evaluator is None:
+            raise RuntimeError("t2m_eval needs the evaluator nets: load_config(overrides={'model.t2m_evaluator.target': 'mld_hip.evaluators.HipT2MEvaluator'})")
+        import numpy as np
+        texts, lengths = list(batch["text"]), [int(x) for x in batch["length"]]
+        motions = batch["motion"].detach().clone().float()
+        B = len(lengths)
+        if self.do_classifier_free_guidance:                                    # mld.py:643-649: uncond half first
+            texts = [""] * len(texts) + ([""] * len(texts) if self.condition == "text_uncond" else texts)
+        text_emb = self.text_encoder(texts)
+        if self.fused and self.vae_type != "no":
+            noise_kw = {} if self.eta == 0.0 else {"seed": seed}
+            joints_rst, feats_rst, _ = self.sample(text_emb.to(motions.device), lengths, init_latents, **noise_kw)
+        else:
+            z = self._diffusion_reverse(text_emb, lengths, init_latents)
+            feats_rst = self.vae.decode(z, lengths) if self.vae_type != "no" else z.permute(1, 0, 2).contiguous()
+            joints_rst = self.feats2joints(feats_rst.detach())
+        motions = motions.to(feats_rst.device)
+        joints_ref = self.feats2joints(motions.contiguous())
+        m_rst, m_ref = self.datamodule.renorm4t2m(feats_rst), self.datamodule.renorm4t2m(motions)      # mld.py:675-677
+        align_idx = np.argsort(lengths)[::-1].copy()                            # mld.py:682
+        idx = torch.from_numpy(align_idx).to(feats_rst.device)
+        ev = self.t2m_evaluator
+        if m_rst.shape[1] == m_ref.shape[1] and 2 * B <= ev.capacity(ev.engine):
+            emb = ev.motion_embed(torch.cat([m_rst, m_ref]).contiguous(), lengths * 2, renorm=False)
+            recons_emb, motion_emb = emb[:B], emb[B:]
+        else:
+            recons_emb, motion_emb = ev.motion_embed(m_rst.contiguous(), lengths, renorm=False), ev.motion_embed(m_ref.contiguous(), lengths, renorm=False)
+        dev = feats_rst.device
+        lat_t = ev.text_embed(batch["word_embs"].detach().float().to(dev), batch["pos_ohot"].detach().float().to(dev), [int(x) for x in batch["text_len"]])
+        return {"m_ref": m_ref[idx], "m_rst": m_rst[idx], "lat_t": lat_t[idx], "lat_m": motion_emb[idx], "lat_rm": recons_emb[idx],
+                "joints_ref": joints_ref, "joints_rst": joints_rst}
 
     # ------------------------------------------------------------------ reference surface
     @torch.no_grad()

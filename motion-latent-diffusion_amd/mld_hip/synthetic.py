@@ -272,6 +272,53 @@ def make_mean_std(nfeats: int = NFEATS) -> Tuple[np.ndarray, np.ndarray]:
     return mean, std
 
 
+def make_mean_std_eval(nfeats: int = NFEATS) -> Tuple[np.ndarray, np.ndarray]:
+    """Stand-ins for the evaluators' own statistics (the reference's ``t2m/.../meta/mean.npy`` / ``std.npy`` that ``renorm4t2m`` reads):
+    close to ``make_mean_std`` but not equal to it, so a renorm that is skipped or uses the wrong pair shows."""
+    mean, std = make_mean_std(nfeats)
+    g = _rng(7, f"mean_std_eval{nfeats}")
+    mean_eval = (mean + 0.05 * g.standard_normal(nfeats)).astype(np.float32)
+    std_eval = (std * g.uniform(0.8, 1.25, nfeats)).astype(np.float32)
+    return mean_eval, std_eval
+
+
+def make_t2m_state_dict(seed: int = 5, nfeats: int = NFEATS) -> Dict[str, np.ndarray]:
+    """Synthetic T2M evaluator weights under their checkpoint names (``t2m_moveencoder.*``, ``t2m_motionencoder.*``, ``t2m_textencoder.*``) at the released
+    widths (the reference's configs/base.yaml: movement 512 / 512, motion GRU 1024 -> 512, word 300, POS 15, text GRU 512 -> 512).  PyTorch's default init
+    ranges (U(-1/sqrt(fan_in), +) for Conv1d / Linear, U(-1/sqrt(H), +) for every GRU tensor), ``hidden`` unit normal, LayerNorm affine perturbed as elsewhere
+    here.  About 60 MB: never committed, regenerated from the seed wherever needed."""
+    sd: Dict[str, np.ndarray] = {}
+
+    def conv(prefix, n_out, n_in):
+        bound = 1.0 / np.sqrt(n_in * 4)
+        sd[f"{prefix}.weight"] = _uniform(seed, f"{prefix}.weight", (n_out, n_in, 4), bound)
+        sd[f"{prefix}.bias"] = _uniform(seed, f"{prefix}.bias", (n_out,), bound)
+
+    def gru(prefix, h, k):
+        bound = 1.0 / np.sqrt(h)
+        for sfx in ("", "_reverse"):
+            sd[f"{prefix}.weight_ih_l0{sfx}"] = _uniform(seed, f"{prefix}.weight_ih_l0{sfx}", (3 * h, k), bound)
+            sd[f"{prefix}.weight_hh_l0{sfx}"] = _uniform(seed, f"{prefix}.weight_hh_l0{sfx}", (3 * h, h), bound)
+            sd[f"{prefix}.bias_ih_l0{sfx}"] = _uniform(seed, f"{prefix}.bias_ih_l0{sfx}", (3 * h,), bound)
+            sd[f"{prefix}.bias_hh_l0{sfx}"] = _uniform(seed, f"{prefix}.bias_hh_l0{sfx}", (3 * h,), bound)
+
+    def tower(prefix, h, n_in):
+        _linear(sd, seed, f"{prefix}.input_emb", h, n_in)
+        gru(f"{prefix}.gru", h, h)
+        sd[f"{prefix}.hidden"] = _rng(seed, f"{prefix}.hidden").standard_normal((2, 1, h)).astype(np.float32)
+        _linear(sd, seed, f"{prefix}.output_net.0", h, 2 * h)
+        _norm(sd, seed, f"{prefix}.output_net.1", h)
+        _linear(sd, seed, f"{prefix}.output_net.3", 512, h)
+
+    conv("t2m_moveencoder.main.0", 512, nfeats - 4)
+    conv("t2m_moveencoder.main.3", 512, 512)
+    _linear(sd, seed, "t2m_moveencoder.out_net", 512, 512)
+    tower("t2m_motionencoder", 1024, 512)
+    _linear(sd, seed, "t2m_textencoder.pos_emb", 300, 15)
+    tower("t2m_textencoder", 512, 300)
+    return sd
+
+
 @dataclass
 class SyntheticBatch:
     text_emb: np.ndarray        # [2B, 1, 768]; rows 0..B-1 = the shared "" (unconditional) embedding
