@@ -484,6 +484,30 @@ typedef struct mldhip_start {
 int mldhip_sample_many_from(mldhip_handle* h, const mldhip_request* reqs, const mldhip_noise_key* keys /* NULL ok at eta = 0 */,
                             const mldhip_start* starts /* [nreq] */, float* const* traj_out_dev /* NULL ok */, int32_t nreq, void* stream);
 
+/* Per-request classifier-free-guidance scale (added at ABI 8 WITHOUT a version bump, as the two entries above were: one more symbol, no struct changed -- callers
+ * detect it by its presence).  mldhip_config.guidance_scale is fixed when the handle is created; here every request of a call may name its own, so one handle (one
+ * set of weight images and workspaces) serves callers who choose guidance, and their requests share a chain.
+ *   guidance_host     [nreq] host floats, or NULL.
+ *                     g_i >= 0 and finite: every motion of request i combines eps = eps_u + g_i * (eps_c - eps_u) with that g_i.  The formula is applied as it stands
+ *                       for every such value: g = 0 is the unconditional prediction, g = 1 the conditional one up to a rounding.  (The reference switches CFG off per
+ *                       MODEL at guidance_scale <= 1 -- mld.py:300 -- not per sample: there is no per-sample switch to reproduce.)
+ *                     g_i < 0 (write -1): the handle's own guidance_scale.
+ *                     NULL, or every entry negative: the call IS mldhip_sample_many_from -- same path, same captured graphs, same launch counts, same bits.
+ *   starts, keys, traj_out_dev   as for mldhip_sample_many_from; starts may be NULL (no request has a source).
+ * MLDHIP_EINVAL: a NaN or infinite entry; a non-negative entry on a handle whose guidance_scale <= 1 (such a model does no CFG, and an action engine then builds no
+ * unconditional rows); a non-negative entry on a MLDHIP_VAE_NONE handle (the diffusion-only variant is out of scope, as it is for trajectories).
+ * A call with any non-negative entry runs as ONE chain over all its motions, also under "many_pipeline" 1 (sum of B <= max_batch): the trajectory rule.  It serves text
+ * and action engines, eta = 0 and eta > 0, with or without trajectories and sources, on every loop family, on the from-forms of the loop kernels: the scale is a field
+ * of the per-motion start table that is uploaded with every call, so on the one-launch loops (persistent and cluster) the captured graph of a shape is replayed with
+ * different values, and the launch-per-GEMM families keep their graph keys (the values are no part of them).  Motions never interact: a motion's result depends on its
+ * own g and not on its neighbours'.
+ * Range contract: the verdict of the finalize probe (mldhip_numeric_info) is for the handle's guidance_scale g_0.  The probe models the amplification of the split-f16
+ * error by guidance as 2 g - 1, so a request above the handle's value scales that error by (2 g_i - 1) / (2 g_0 - 1).  The engine does not refuse such a request;
+ * the non-finite counter (mldhip_numeric_status) applies as ever. */
+int mldhip_sample_many_guided(mldhip_handle* h, const mldhip_request* reqs, const mldhip_noise_key* keys /* NULL ok at eta = 0 */,
+                              const mldhip_start* starts /* NULL ok */, float* const* traj_out_dev /* NULL ok */,
+                              const float* guidance_host /* [nreq] or NULL */, int32_t nreq, void* stream);
+
 /* Replaces: MldDenoiser.forward(sample, timestep, encoder_hidden_states)[0]
  * (mld/models/architectures/mld_denoiser.py:135-228).  sample [R,1,D], text [R,1,text_dim],
  * out [R,1,D]; any integer timestep in [0, num_train_timesteps). */

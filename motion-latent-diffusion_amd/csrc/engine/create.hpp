@@ -405,7 +405,7 @@ int create_engine(const mldhip_config& cfg, int device, int num_cus, mldhip_hand
         hipMemset(x.starts, 0, Bm * sizeof(StartRow)) != hipSuccess) return fail_create("hipMalloc(lens) failed");
     x.keys_host.assign(Bm, NoiseKey{0ull, 0ll});
     x.traj_host.assign(Bm, TrajRow{nullptr, 0ll});
-    x.starts_host.assign(Bm, StartRow{nullptr, 0, 0, 0.f, 0.f, {0, 0}});
+    x.starts_host.assign(Bm, StartRow{nullptr, 0, 0, 0.f, 0.f, 0.f, 0});
 #if !defined(MLDHIP_SIM)
     for (hipEvent_t* ev : x.events())
       if (hipEventCreateWithFlags(ev, hipEventDisableTiming) != hipSuccess) return fail_create("event create failed");

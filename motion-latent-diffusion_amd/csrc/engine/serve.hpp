@@ -149,18 +149,23 @@ int upload_traj(E* e, const mldhip_request* rq, float* const* traj, int nreq, hi
 }
 
 // The start table of a coalesced call into the bound context's array (mldhip_sample_many_from): motion k of request i gets {src_i + k * D, first_step_i, noised_i}
-// and the two add_noise coefficients of its first step -- or the all-zero entry (start from noise at step 0) when the request has no source.  Host copy + upload
-// with every call, like the trajectory table: the kernels never see a caller pointer or a first step as a launch argument.  Returns the call's smallest first step.
-int upload_starts(E* e, const mldhip_request* rq, const mldhip_start* starts, int nreq, hipStream_t stream, int* step0) {
+// and the two add_noise coefficients of its first step -- or the all-zero entry (start from noise at step 0) when the request has no source (`starts` == nullptr: none
+// has one).  Every entry also carries the motion's guidance scale (mldhip_sample_many_guided): guid[i] where it is given and not negative, otherwise the value the plain
+// forms get as their launch argument -- the from-forms read it here, so a call without `guid` computes the same expression on the same number as before.  Host copy +
+// upload with every call, like the trajectory table: the kernels never see a caller pointer, a first step or a scale as a launch argument.  Returns the call's smallest
+// first step.
+int upload_starts(E* e, const mldhip_request* rq, const mldhip_start* starts, const float* guid, int nreq, hipStream_t stream, int* step0) {
   WsContext& x = e->ctxs[e->cur_ctx];
   const long long D = (long long)e->cfg.latent_size * e->cfg.latent_dim;
+  const float g0 = e->cfg.guidance_scale > 1.0f ? e->cfg.guidance_scale : 1.0f;      // enqueue_sample's `guidance`
   int o = 0, lo = e->cfg.num_inference_steps - 1;
   for (int i = 0; i < nreq; ++i) {
-    const mldhip_start& s = starts[i];
+    const mldhip_start s = starts ? starts[i] : mldhip_start{nullptr, 0, 0};
     const DdimCoef k = ddim_coef(e, e->timesteps[s.first_step]);
+    const float g = guid && guid[i] >= 0.0f ? guid[i] : g0;
     lo = std::min(lo, (int)s.first_step);
     for (int m = 0; m < rq[i].B; ++m, ++o)
-      x.starts_host[o] = s.src_latents_dev ? StartRow{s.src_latents_dev + m * D, s.first_step, s.noised, k.sqrt_at, k.sqrt_1mat, {0, 0}} : StartRow{nullptr, 0, 0, 0.f, 0.f, {0, 0}};
+      x.starts_host[o] = s.src_latents_dev ? StartRow{s.src_latents_dev + m * D, s.first_step, s.noised, k.sqrt_at, k.sqrt_1mat, g, 0} : StartRow{nullptr, 0, 0, 0.f, 0.f, g, 0};
   }
   HIP_TRY(e, hipMemcpyAsync(e->starts_dev, x.starts_host.data(), (size_t)o * sizeof(StartRow), hipMemcpyHostToDevice, stream));
   *step0 = lo;
@@ -441,9 +446,11 @@ int scatter_results(Ctx& c, const mldhip_request* rq, int nreq, const std::vecto
 
 // `traj` (or nullptr): per request, the [steps][B_i][D] buffer that receives the latents after every scheduler step (mldhip_sample_many_traj); a call that asks
 // for any runs as one chain, also under "many_pipeline" 1.  `starts` (or nullptr): per request, where its motions enter the loop (mldhip_sample_many_from; checked by
-// the caller); a call with any source is one chain as well, on the from-forms of the loop kernels
+// the caller); a call with any source is one chain as well, on the from-forms of the loop kernels.  `guid` (or nullptr): per request, its guidance scale or a negative
+// value for the handle's own (mldhip_sample_many_guided; the caller passes it only when some entry is not negative): the same from-forms, which take every motion's
+// scale from its start entry -- a guided call without sources is a from-call whose starts are all trivial
 int sample_many_impl(E* e, const mldhip_request* rq, int nreq, hipStream_t stream, const mldhip_noise_key* keys = nullptr, float* const* traj = nullptr,
-                     const mldhip_start* starts = nullptr) {
+                     const mldhip_start* starts = nullptr, const float* guid = nullptr) {
   if (!e->finalized) return e->fail(MLDHIP_ESTATE, "mldhip_sample_many before mldhip_finalize_weights");
   heal_cluster(e);
   const bool action = is_action(e);
@@ -468,7 +475,7 @@ int sample_many_impl(E* e, const mldhip_request* rq, int nreq, hipStream_t strea
     return e->fail(MLDHIP_ESTATE, "mldhip_sample_many needs denoiser.*, vae.decoder.* (and mean/std for joints) loaded");
   bool want_t = false;
   for (int i = 0; traj && i < nreq; ++i) want_t = want_t || traj[i];
-  bool want_s = false;
+  bool want_s = guid != nullptr;
   for (int i = 0; starts && i < nreq; ++i) want_s = want_s || starts[i].src_latents_dev;
   if (e->many_pipeline && nreq >= 2 && e->ctxs.size() >= 2 && !want_t && !want_s) {
     bool ok = true;
@@ -483,7 +490,7 @@ int sample_many_impl(E* e, const mldhip_request* rq, int nreq, hipStream_t strea
   if (keys) if (int rc = upload_keys(e, rq, keys, 0, nreq, stream)) return rc;
   if (want_t) if (int rc = upload_traj(e, rq, traj, nreq, stream)) return rc;
   int step0 = 0;
-  if (want_s) if (int rc = upload_starts(e, rq, starts, nreq, stream, &step0)) return rc;
+  if (want_s) if (int rc = upload_starts(e, rq, starts, guid, nreq, stream, &step0)) return rc;
   if (action) {
     // stage_actions' layout for the gathered batch, built on the host (the requests' labels are not contiguous): one copy
     std::vector<int32_t> lab(2 * (size_t)Btot, 0);
@@ -494,7 +501,7 @@ int sample_many_impl(E* e, const mldhip_request* rq, int nreq, hipStream_t strea
   Ctx cio{e, stream};
   std::vector<const float*> lat_of;
   if (want_s) {      // a resumed request may come without init_latents: its source stands in for the gather (same shape; the from-forms never read those rows)
-    for (int i = 0; i < nreq; ++i) lat_of.push_back(rq[i].init_latents_dev ? rq[i].init_latents_dev : starts[i].src_latents_dev);
+    for (int i = 0; i < nreq; ++i) lat_of.push_back(rq[i].init_latents_dev || !starts ? rq[i].init_latents_dev : starts[i].src_latents_dev);
   }
   if (int rc = gather_requests(cio, rq, nreq, Btot, want_s ? lat_of.data() : nullptr)) return rc;
   const float* text = action ? nullptr : e->text_in;

@@ -68,8 +68,9 @@ struct TrajRow { float* row0; long long step_stride; };
 // Start entry of one motion of a call (mldhip_sample_many_from): src == NULL: the motion starts from init_latents * init_noise_sigma at step 0 (first_step is 0);
 // otherwise the loop state in front of step first_step is c_src * src + c_noise * init_latents (noised == 0: diffusers' add_noise at timesteps[first_step]; the
 // two coefficients are the step's sqrt(ab_t), sqrt(1 - ab_t), the first two words of its DdimCoef) or src as it is (noised == 1), and steps below first_step leave
-// the motion alone.  src points at the motion's own row of the caller's buffer.
-struct StartRow { const float* src; int first_step; int noised; float c_src, c_noise; int pad[2]; };
+// the motion alone.  src points at the motion's own row of the caller's buffer.  guidance: the motion's classifier-free-guidance scale (mldhip_sample_many_guided;
+// the handle's own for a request that names none) -- the from-forms of the loop kernels read it here and not from their launch arguments.
+struct StartRow { const float* src; int first_step; int noised; float c_src, c_noise; float guidance; int pad; };
 static_assert(sizeof(StartRow) == 32, "StartRow is uploaded as an array");
 
 // init_chain_kernel for a call that starts from sources (mldhip_sample_many_from): the same token rows with each motion's own start state (StartRow) and the time row of the

@@ -291,6 +291,7 @@
   // ---- prologue: latents, parameters of layer 0, the first step's rows, the ring; placement census when plain stores were asked for
   int step0 = 0;                                 // FROM: the first step this cluster runs
   [[maybe_unused]] int myf = 0;                  // FROM: first step of this wave's motion (s0 + wave; a ragged cluster's missing motions repeat the last real one)
+  float myg = p.guidance;                        // FROM: guidance scale of this wave's motion, from its StartRow (global index: s_base included); else the launch's
   if constexpr (FROM) {
     const int c = tid >> 6, c4 = tid & 63;
     int s = s0 + c;
@@ -307,6 +308,7 @@
     }
     st4(lats + c * 256 + c4 * 4, v);
     myf = st.first_step;
+    myg = st.guidance;
     step0 = p.n - 1;
     for (int k = 0; k < 8; ++k)
       if (s0 + k < p.s_end) { const int fk = p.starts[s0 + k].first_step; step0 = fk < step0 ? fk : step0; }
@@ -747,7 +749,7 @@
           if (s0 + wave < p.s_end) latent_noise4(p.keys[s0 + wave], (unsigned)step, lane, z);
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
-            const float eps = eu[i] + p.guidance * (ec[i] - eu[i]);
+            const float eps = eu[i] + myg * (ec[i] - eu[i]);
             const float x0 = (xtv[i] - s1mat * eps) / sat;
             nv[i] = sap * x0 + ce * eps;
             nv[i] += sg * z[i];
@@ -755,7 +757,7 @@
         } else {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          const float eps = eu[i] + p.guidance * (ec[i] - eu[i]);
+          const float eps = eu[i] + myg * (ec[i] - eu[i]);
           const float x0 = (xtv[i] - s1mat * eps) / sat;
           nv[i] = sap * x0 + s1map * eps;
         }

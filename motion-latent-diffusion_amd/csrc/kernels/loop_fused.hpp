@@ -461,6 +461,7 @@ __global__ __launch_bounds__(512, 2) void den_loop_kernel(LoopArgs p) {
   // ---- prologue: latents; first step's token rows; the first kLoopRing items into the ring
   int step0 = 0;                                   // FROM: the first step this workgroup runs = the smallest first step of its real motions
   [[maybe_unused]] int myf = 0;                    // FROM: first step of this lane's motion (row r & 7; rows beyond B repeat motion B - 1, as everywhere)
+  float myg = p.guidance;                          // FROM: guidance scale of this lane's motion, from its StartRow (mldhip_sample_many_guided); else the launch's
   if constexpr (FROM) {
     const int c = tid >> 6, c4 = tid & 63;
     int s = s0 + c;
@@ -483,6 +484,7 @@ __global__ __launch_bounds__(512, 2) void den_loop_kernel(LoopArgs p) {
     int sm_ = s0 + (r & 7);
     sm_ = sm_ < p.B ? sm_ : p.B - 1;
     myf = p.starts[sm_].first_step;
+    myg = p.starts[sm_].guidance;
   } else {
     const int c = tid >> 6, c4 = tid & 63;
     int s = s0 + c;
@@ -804,7 +806,7 @@ __global__ __launch_bounds__(512, 2) void den_loop_kernel(LoopArgs p) {
 #pragma unroll
               for (int i = 0; i < 4; ++i) {
                 const float eu = x[cb][0][i];
-                const float eps = eu + p.guidance * (ec[i] - eu);
+                const float eps = eu + myg * (ec[i] - eu);
                 const float x0 = (xtv[i] - s1mat * eps) / sat;
                 nv[i] = sap * x0 + ce * eps;
                 nv[i] += sg * z[i];
@@ -813,7 +815,7 @@ __global__ __launch_bounds__(512, 2) void den_loop_kernel(LoopArgs p) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
               const float eu = x[cb][0][i];
-              const float eps = eu + p.guidance * (ec[i] - eu);
+              const float eps = eu + myg * (ec[i] - eu);
               const float x0 = (xtv[i] - s1mat * eps) / sat;
               nv[i] = sap * x0 + s1map * eps;
             }

@@ -402,7 +402,9 @@ __device__ __forceinline__ void den_final_step_body(const FinalArgs& f, float* _
   const int b = blockIdx.x, d = threadIdx.x, R = 2 * B;
   const float eu = final_row_value(f, b, d, sh);
   const float ec = final_row_value(f, B + b, d, sh);
-  const float eps = eu + guidance * (ec - eu);
+  float g = guidance;
+  if constexpr (FROM) g = starts[b].guidance;      // the motion's own scale (mldhip_sample_many_guided; block-uniform: one block per motion)
+  const float eps = eu + g * (ec - eu);
   const float x = lat[(long long)b * 256 + d];
   const float x0 = (x - c.sqrt_1mat * eps) / c.sqrt_at;
   float xn;

@@ -430,20 +430,14 @@ int mldhip_sample_many_traj(mldhip_handle* e, const mldhip_request* reqs, const 
   return sample_many_impl(e, reqs, nreq, (hipStream_t)stream_, eta_on(e) ? keys : nullptr, any ? traj_out_dev : nullptr);
 }
 
-int mldhip_sample_many_from(mldhip_handle* e, const mldhip_request* reqs, const mldhip_noise_key* keys, const mldhip_start* starts, float* const* traj_out_dev,
-                            int32_t nreq, void* stream_) {
-  if (!e) return MLDHIP_EINVAL;
-  bool any = false;
-  for (int i = 0; starts && nreq >= 1 && nreq <= 64 && i < nreq; ++i) any = any || starts[i].src_latents_dev || starts[i].first_step != 0 || starts[i].noised != 0;
-  // no source anywhere (and nothing else set): the call IS mldhip_sample_many_traj -- same checks, same path, same captured graphs
-  if (!any) return mldhip_sample_many_traj(e, reqs, keys, traj_out_dev, nreq, stream_);
-  DeviceGuard dg(e->device);
-  if (!reqs) return e->fail(MLDHIP_EINVAL, "1..64 requests expected");
-  if (is_novae(e)) return e->fail(MLDHIP_EINVAL, "mldhip_sample_many_from: the diffusion-only variant has no latent to start from (its loop state is the raw motion [B, T, nfeats])");
+// shared body of mldhip_sample_many_from / mldhip_sample_many_guided behind their trivial cases: `starts` may be NULL (no request has a source), `guid` is non-NULL
+// only when some request names a guidance scale of its own
+static int sample_many_from_checked(mldhip_handle* e, const mldhip_request* reqs, const mldhip_noise_key* keys, const mldhip_start* starts, float* const* traj_out_dev,
+                                    const float* guid, int32_t nreq, void* stream_) {
   const int n = e->cfg.num_inference_steps;
   bool traj = false;
   for (int i = 0; i < nreq; ++i) {
-    const mldhip_start& s = starts[i];
+    const mldhip_start s = starts ? starts[i] : mldhip_start{nullptr, 0, 0};
     if (s.noised != 0 && s.noised != 1) return e->fail(MLDHIP_EINVAL, "starts[%d].noised = %d (0: a clean source, 1: the loop state at first_step)", i, (int)s.noised);
     if (s.first_step < 0 || s.first_step >= n) return e->fail(MLDHIP_EINVAL, "starts[%d].first_step = %d outside [0, num_inference_steps = %d)", i, (int)s.first_step, n);
     if (!s.src_latents_dev && s.first_step != 0) return e->fail(MLDHIP_EINVAL, "starts[%d]: first_step = %d without a source (a start from noise begins at step 0)", i, (int)s.first_step);
@@ -457,7 +451,42 @@ int mldhip_sample_many_from(mldhip_handle* e, const mldhip_request* reqs, const 
   if (eta_on(e) && !keys) return e->fail(MLDHIP_EINVAL, "keys is NULL on a handle with eta > 0 (one mldhip_noise_key per request)");
   for (int i = 0; keys && i < nreq; ++i)
     if (keys[i].first_index < 0) return e->fail(MLDHIP_EINVAL, "keys[%d].first_index %lld is negative", i, (long long)keys[i].first_index);
-  return sample_many_impl(e, reqs, nreq, (hipStream_t)stream_, eta_on(e) ? keys : nullptr, traj ? traj_out_dev : nullptr, starts);
+  return sample_many_impl(e, reqs, nreq, (hipStream_t)stream_, eta_on(e) ? keys : nullptr, traj ? traj_out_dev : nullptr, starts, guid);
+}
+
+int mldhip_sample_many_from(mldhip_handle* e, const mldhip_request* reqs, const mldhip_noise_key* keys, const mldhip_start* starts, float* const* traj_out_dev,
+                            int32_t nreq, void* stream_) {
+  if (!e) return MLDHIP_EINVAL;
+  bool any = false;
+  for (int i = 0; starts && nreq >= 1 && nreq <= 64 && i < nreq; ++i) any = any || starts[i].src_latents_dev || starts[i].first_step != 0 || starts[i].noised != 0;
+  // no source anywhere (and nothing else set): the call IS mldhip_sample_many_traj -- same checks, same path, same captured graphs
+  if (!any) return mldhip_sample_many_traj(e, reqs, keys, traj_out_dev, nreq, stream_);
+  DeviceGuard dg(e->device);
+  if (!reqs) return e->fail(MLDHIP_EINVAL, "1..64 requests expected");
+  if (is_novae(e)) return e->fail(MLDHIP_EINVAL, "mldhip_sample_many_from: the diffusion-only variant has no latent to start from (its loop state is the raw motion [B, T, nfeats])");
+  return sample_many_from_checked(e, reqs, keys, starts, traj_out_dev, nullptr, nreq, stream_);
+}
+
+int mldhip_sample_many_guided(mldhip_handle* e, const mldhip_request* reqs, const mldhip_noise_key* keys, const mldhip_start* starts, float* const* traj_out_dev,
+                              const float* guidance_host, int32_t nreq, void* stream_) {
+  if (!e) return MLDHIP_EINVAL;
+  bool any = false;
+  for (int i = 0; guidance_host && nreq >= 1 && nreq <= 64 && i < nreq; ++i) {
+    if (!std::isfinite(guidance_host[i])) {
+      DeviceGuard dg(e->device);
+      return e->fail(MLDHIP_EINVAL, "guidance_host[%d] is not finite", i);
+    }
+    any = any || guidance_host[i] >= 0.0f;
+  }
+  // no request names a scale: the call IS mldhip_sample_many_from -- same checks, same path, same captured graphs
+  if (!any) return mldhip_sample_many_from(e, reqs, keys, starts, traj_out_dev, nreq, stream_);
+  DeviceGuard dg(e->device);
+  if (!reqs) return e->fail(MLDHIP_EINVAL, "1..64 requests expected");
+  if (is_novae(e)) return e->fail(MLDHIP_EINVAL, "mldhip_sample_many_guided: per-request guidance serves the latent models (the diffusion-only variant is out of scope)");
+  if (!(e->cfg.guidance_scale > 1.0f))
+    return e->fail(MLDHIP_EINVAL, "mldhip_sample_many_guided: the handle's guidance_scale is %g (<= 1): such a model does no classifier-free guidance (an action engine builds no unconditional rows)",
+                   (double)e->cfg.guidance_scale);
+  return sample_many_from_checked(e, reqs, keys, starts, traj_out_dev, guidance_host, nreq, stream_);
 }
 
 int mldhip_sample(mldhip_handle* e, const float* text_emb_dev, const float* init_latents_dev, const int32_t* lengths_host,

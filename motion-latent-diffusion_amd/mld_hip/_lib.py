@@ -92,6 +92,8 @@ _SYMBOLS = {
     "mldhip_sample_many_traj": (C.c_int, [C.c_void_p, C.POINTER(Request), C.POINTER(NoiseKey), C.POINTER(C.c_void_p), C.c_int32, C.c_void_p]),
     "mldhip_sample_many_from": (C.c_int, [C.c_void_p, C.POINTER(Request), C.POINTER(NoiseKey), C.POINTER(Start), C.POINTER(C.c_void_p), C.c_int32,
                                           C.c_void_p]),
+    "mldhip_sample_many_guided": (C.c_int, [C.c_void_p, C.POINTER(Request), C.POINTER(NoiseKey), C.POINTER(Start), C.POINTER(C.c_void_p),
+                                            C.POINTER(C.c_float), C.c_int32, C.c_void_p]),
     "mldhip_denoiser_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "mldhip_sample_action": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
@@ -302,6 +304,23 @@ class Engine:
         tr = (C.c_void_p * len(requests))(*[_ptr(q.get("traj_out")) or None for q in requests])
         st = (Start * len(requests))(*[Start(_ptr(q.get("src_latents")) or None, int(q.get("first_step", 0)), int(q.get("noised", 0))) for q in requests])
         self._check(self.lib.mldhip_sample_many_from(self._h, arr, ks, st, tr, len(requests), stream))
+
+    def sample_many_guided(self, requests: Sequence[dict], keys: Optional[Sequence] = None, stream: int = 0):
+        """``sample_many_from`` whose requests may name their own classifier-free-guidance scale (mldhip_sample_many_guided).  A request dict may
+        carry ``guidance``, a float >= 0: its motions combine eps_u + g * (eps_c - eps_u) with that g (0: the unconditional prediction, 1: the
+        conditional one up to a rounding); without it (or None, or a negative value) the handle's ``guidance_scale`` applies.  The ``src_latents`` /
+        ``first_step`` / ``noised`` and ``traj_out`` keys of ``sample_many_from`` are taken as there.  Without any ``guidance`` the call is
+        ``sample_many_from``.  The handle must have been created with ``guidance_scale`` > 1."""
+        if not hasattr(self.lib, "mldhip_sample_many_guided"):
+            raise MldHipError(-2, "this libmldhip has no mldhip_sample_many_guided")
+        if keys is not None and len(keys) != len(requests):
+            raise ValueError("one (seed, first_index) key per request")
+        arr, keep = self._requests(requests)
+        ks = None if keys is None else (NoiseKey * len(keys))(*[NoiseKey(int(s) & 0xFFFFFFFFFFFFFFFF, int(f)) for s, f in keys])
+        tr = (C.c_void_p * len(requests))(*[_ptr(q.get("traj_out")) or None for q in requests])
+        st = (Start * len(requests))(*[Start(_ptr(q.get("src_latents")) or None, int(q.get("first_step", 0)), int(q.get("noised", 0))) for q in requests])
+        gs = (C.c_float * len(requests))(*[-1.0 if q.get("guidance") is None else float(q["guidance"]) for q in requests])
+        self._check(self.lib.mldhip_sample_many_guided(self._h, arr, ks, st, tr, gs, len(requests), stream))
 
     def _requests(self, requests: Sequence[dict]):
         arr = (Request * len(requests))()

@@ -146,14 +146,15 @@ class MLD(nn.Module):
     @torch.no_grad()
     def sample(self, text_emb: torch.Tensor, lengths: List[int], init_latents: Optional[torch.Tensor] = None, seed: Optional[int] = None,
                first_index: int = 0, return_trajectory: bool = False, src_latents: Optional[torch.Tensor] = None, first_step: int = 0,
-               noised: bool = False):
+               noised: bool = False, guidance_scale: Optional[float] = None):
         """text_emb [2B, 1, 768] (uncond half first) -> (joints [B,T,njoints,3], feats [B,T,nfeats], latents [B,1,D]) on device.
         src_latents [B, 1, D] (mldhip_sample_many_from): the loop starts at scheduler step `first_step` from the source noised with init_latents to
         that step's timestep (`noised` False), or from the source as it is (`noised` True: it already is the loop state there); trajectory rows
         below first_step are left as allocated.
         eta > 0: the step noise of motion m is the engine's Philox stream keyed (seed, first_index + m); `seed` None = drawn from torch's
         generator.  return_trajectory: a fourth result, the latents after every scheduler step [steps, B, D] (mldhip_sample_many_traj; its last
-        row is `latents`)."""
+        row is `latents`).  guidance_scale: this call's classifier-free-guidance scale instead of cfg.model.guidance_scale (mldhip_sample_many_guided:
+        eps_u + g (eps_c - eps_u) for any g >= 0); None = the model's own, on the call sites of a model without the keyword."""
         lengths = [int(x) for x in lengths]
         B, T = len(lengths), max(lengths)
         dev = text_emb.device
@@ -170,12 +171,18 @@ class MLD(nn.Module):
         feats = torch.empty(B, T, self.nfeats, device=dev)
         joints = torch.empty(B, T, self.njoints, 3, device=dev)
         seed = self._noise_seed(seed)
-        if src_latents is not None:
-            req = dict(text_emb=text_emb, init_latents=init_latents, lengths=lengths, latents_out=lat, feats_out=feats, joints_out=joints,
-                       src_latents=src_latents.to(dev).float().contiguous(), first_step=int(first_step), noised=int(bool(noised)))
+        if src_latents is not None or guidance_scale is not None:
+            req = dict(text_emb=text_emb, init_latents=init_latents, lengths=lengths, latents_out=lat, feats_out=feats, joints_out=joints)
+            if src_latents is not None:
+                req.update(src_latents=src_latents.to(dev).float().contiguous(), first_step=int(first_step), noised=int(bool(noised)))
             if return_trajectory:
                 req["traj_out"] = self._traj_buffer(eng, B, dev)
-            eng.sample_many_from([req], None if seed is None else [(seed, int(first_index))], _engine.current_stream_handle(text_emb))
+            keys = None if seed is None else [(seed, int(first_index))]
+            if guidance_scale is not None:
+                req["guidance"] = float(guidance_scale)
+                eng.sample_many_guided([req], keys, _engine.current_stream_handle(text_emb))
+            else:
+                eng.sample_many_from([req], keys, _engine.current_stream_handle(text_emb))
             return (joints, feats, lat, req["traj_out"]) if return_trajectory else (joints, feats, lat)
         if return_trajectory:
             traj = self._traj_buffer(eng, B, dev)
@@ -192,7 +199,7 @@ class MLD(nn.Module):
 
     @torch.no_grad()
     def sample_many(self, requests, init_latents=None, pipeline: bool = False, seed: Optional[int] = None, first_index: int = 0,
-                    return_trajectory: bool = False, src_latents=None, first_step=None, noised=None):
+                    return_trajectory: bool = False, src_latents=None, first_step=None, noised=None, guidance=None):
         """Several independent text-to-motion requests as ONE engine call (``mldhip_sample_many``: one reverse-diffusion chain +
         one decode over all of them; the engine needs ``max_batch >= total motions``).  `requests` = [(text_emb [2B_i,1,768],
         lengths_i), ...]; returns [(joints_i, feats_i, latents_i), ...] on device, each shaped as ``sample`` would return it.
@@ -205,7 +212,10 @@ class MLD(nn.Module):
         (mldhip_sample_many_traj; such a call runs as one chain, also with ``pipeline=True``).
 
         ``src_latents`` / ``first_step`` / ``noised``: one entry per request (a tensor [B_i, 1, D] or None; an int; a bool) -- where each request
-        enters the reverse loop (mldhip_sample_many_from, see ``sample``); such a call runs as one chain as well."""
+        enters the reverse loop (mldhip_sample_many_from, see ``sample``); such a call runs as one chain as well.
+
+        ``guidance``: one entry per request, a float >= 0 or None (the model's own scale) -- requests with different classifier-free-guidance scales
+        in one chain on one engine (mldhip_sample_many_guided).  None: the call sites above, unchanged."""
         if self.vae_type == "no" or self.condition == "action":
             raise NotImplementedError("sample_many serves the text-to-motion latent model")
         eng = self._engine()
@@ -230,6 +240,8 @@ class MLD(nn.Module):
             if src_latents is not None and src_latents[i] is not None:
                 reqs[-1].update(src_latents=src_latents[i].to(dev).float().contiguous(), first_step=int(first_step[i]) if first_step is not None else 0,
                                 noised=int(bool(noised[i])) if noised is not None else 0)
+            if guidance is not None and guidance[i] is not None:
+                reqs[-1]["guidance"] = float(guidance[i])
             if return_trajectory:
                 reqs[-1]["traj_out"] = self._traj_buffer(eng, B, dev)
                 outs.append((joints, feats, lat, reqs[-1]["traj_out"]))
@@ -239,7 +251,9 @@ class MLD(nn.Module):
             eng.set_option("many_pipeline", 1)
         seed = self._noise_seed(seed)
         try:
-            if any("src_latents" in q for q in reqs):
+            if any("guidance" in q for q in reqs):
+                eng.sample_many_guided(reqs, None if seed is None else self._keys(seed, reqs, first_index), stream)
+            elif any("src_latents" in q for q in reqs):
                 eng.sample_many_from(reqs, None if seed is None else self._keys(seed, reqs, first_index), stream)
             elif return_trajectory:
                 eng.sample_many_traj(reqs, None if seed is None else self._keys(seed, reqs, first_index), stream)
@@ -294,9 +308,10 @@ class MLD(nn.Module):
 
     @torch.no_grad()
     def sample_action(self, actions, lengths: List[int], init_latents: Optional[torch.Tensor] = None, device=None, seed: Optional[int] = None,
-                      first_index: int = 0, return_trajectory: bool = False):
+                      first_index: int = 0, return_trajectory: bool = False, guidance_scale: Optional[float] = None):
         """Action labels [B] / [B, 1] -> (feats [B, T, nfeats], latents [B, 1, D]) on device: ONE mldhip_sample_action call.
-        return_trajectory: a third result, the latents after every scheduler step [steps, B, D] (mldhip_sample_many_traj)."""
+        return_trajectory: a third result, the latents after every scheduler step [steps, B, D] (mldhip_sample_many_traj).
+        guidance_scale: this call's classifier-free-guidance scale (mldhip_sample_many_guided); None = the model's own."""
         lengths = [int(x) for x in lengths]
         acts = [int(a) for a in (actions.reshape(-1).tolist() if torch.is_tensor(actions) else list(actions))]
         B, T = len(lengths), max(lengths)
@@ -308,6 +323,12 @@ class MLD(nn.Module):
         lat = torch.empty(B, self.latent_dim[0], self.latent_dim[-1], device=dev)
         feats = torch.empty(B, T, self.nfeats, device=dev)
         seed = self._noise_seed(seed)
+        if guidance_scale is not None:
+            req = dict(actions=acts, init_latents=init_latents, lengths=lengths, latents_out=lat, feats_out=feats, guidance=float(guidance_scale))
+            if return_trajectory:
+                req["traj_out"] = self._traj_buffer(eng, B, dev)
+            eng.sample_many_guided([req], None if seed is None else [(seed, int(first_index))], _engine.current_stream_handle(init_latents))
+            return (feats, lat, req["traj_out"]) if return_trajectory else (feats, lat)
         if return_trajectory:
             traj = self._traj_buffer(eng, B, dev)
             eng.sample_many_traj([dict(actions=acts, init_latents=init_latents, lengths=lengths, latents_out=lat, feats_out=feats, traj_out=traj)],
@@ -321,10 +342,11 @@ class MLD(nn.Module):
         return feats, lat
 
     @torch.no_grad()
-    def sample_many_action(self, requests, init_latents=None, device=None, seed: Optional[int] = None, first_index: int = 0):
+    def sample_many_action(self, requests, init_latents=None, device=None, seed: Optional[int] = None, first_index: int = 0, guidance=None):
         """Several action-to-motion requests as ONE engine call (``mldhip_sample_many`` with ``actions_host``): `requests` =
         [(actions_i, lengths_i), ...] -> [(feats_i [B_i, T_i, nfeats], latents_i), ...] on device; the engine needs
-        ``max_batch >= total motions`` (four bs-256 requests per call: 30.0 k motions/s against 5.9 k one call at a time, bench.py)."""
+        ``max_batch >= total motions`` (four bs-256 requests per call: 30.0 k motions/s against 5.9 k one call at a time, bench.py).
+        ``guidance``: one classifier-free-guidance scale per request or None, as for ``sample_many``."""
         if self.condition != "action":
             raise NotImplementedError("sample_many_action serves the action-conditioned model")
         eng = self._engine()
@@ -341,9 +363,13 @@ class MLD(nn.Module):
             feats = torch.empty(B, T, self.nfeats, device=dev)
             keep.append(lat0)
             reqs.append(dict(actions=acts, init_latents=lat0, lengths=lengths, latents_out=lat, feats_out=feats))
+            if guidance is not None and guidance[i] is not None:
+                reqs[-1]["guidance"] = float(guidance[i])
             outs.append((feats, lat))
         seed = self._noise_seed(seed)
-        if seed is None:
+        if any("guidance" in q for q in reqs):
+            eng.sample_many_guided(reqs, None if seed is None else self._keys(seed, reqs, first_index), _engine.current_stream_handle(keep[0]))
+        elif seed is None:
             eng.sample_many(reqs, _engine.current_stream_handle(keep[0]))
         else:
             eng.sample_many_seeded(reqs, self._keys(seed, reqs, first_index), _engine.current_stream_handle(keep[0]))
@@ -407,11 +433,16 @@ class MLD(nn.Module):
     # ------------------------------------------------------------------ reference surface
     @torch.no_grad()
     def forward(self, batch, init_latents: Optional[torch.Tensor] = None, step_noise: Optional[torch.Tensor] = None, seed: Optional[int] = None,
-                first_index: int = 0):
+                first_index: int = 0, guidance_scale=None):
         """mld.py:216-265.  Stochastic DDIM (cfg.model.scheduler.eta > 0): the fused path draws the engine's Philox stream keyed (seed,
         first_index + m) -- `seed` None = drawn from torch's generator; the modular path draws torch.randn, or takes step_noise [steps, B, 1, D]
-        (the fused path's draws reproduce it: include/mldhip.h "Noise contract")."""
+        (the fused path's draws reproduce it: include/mldhip.h "Noise contract").
+        guidance_scale (None: batch["guidance_scale"] if the batch has one): a float for the whole batch or a sequence with one value per prompt
+        (fused latent models; mldhip_sample_many_guided).  A sequence becomes ONE engine call of one request per maximal run of equal values; the
+        noise keys follow the motions (``_keys``), so a motion's draws do not depend on how the batch is split."""
         texts, lengths = list(batch["text"]), list(batch["length"])
+        if guidance_scale is None:
+            guidance_scale = batch.get("guidance_scale") if hasattr(batch, "get") else None
         if self.do_classifier_free_guidance:                                    # mld.py:224-230: uncond half first
             texts = [""] * len(texts) + ([""] * len(texts) if self.condition == "text_uncond" else texts)
         text_emb = self.text_encoder(texts)
@@ -422,7 +453,11 @@ class MLD(nn.Module):
                 z = self._diffusion_reverse(text_emb, lengths, init_latents, step_noise)
                 joints = self.feats2joints(z.permute(1, 0, 2).contiguous())     # mld.py:241-242: "decode" is a permute
             return remove_padding(joints.detach().cpu(), lengths)
-        if self.fused:
+        if guidance_scale is not None and not self.fused:
+            raise NotImplementedError("guidance_scale per call serves the fused latent models")
+        if self.fused and guidance_scale is not None:
+            joints = self._forward_guided(text_emb, lengths, init_latents, seed, first_index, guidance_scale)
+        elif self.fused:
             noise_kw = {} if self.eta == 0.0 else {"seed": seed, "first_index": first_index}      # (eta = 0: the call of the deterministic path, unchanged)
             joints, _, _ = self.sample(text_emb, lengths, init_latents, **noise_kw)
         else:
@@ -430,6 +465,29 @@ class MLD(nn.Module):
             feats = self.vae.decode(z, lengths)
             joints = self.feats2joints(feats.detach())
         return remove_padding(joints.detach().cpu(), lengths)                   # mld.py:264-265
+
+    def _forward_guided(self, text_emb, lengths, init_latents, seed, first_index, guidance_scale):
+        """forward's fused call under a guidance scale of the call's own -> joints [B, Tmax, njoints, 3]: a float is one ``sample``; a per-prompt
+        sequence one ``sample_many`` of one request per maximal run of equal values (motion order kept, so ``_keys`` gives every motion its own key)."""
+        noise_kw = {} if self.eta == 0.0 else {"seed": seed, "first_index": first_index}
+        if isinstance(guidance_scale, (int, float)) or (torch.is_tensor(guidance_scale) and guidance_scale.dim() == 0):
+            return self.sample(text_emb, lengths, init_latents, guidance_scale=float(guidance_scale), **noise_kw)[0]
+        gs = [float(g) for g in guidance_scale]
+        B = len(lengths)
+        if len(gs) != B:
+            raise ValueError(f"guidance_scale has {len(gs)} entries for {B} prompts")
+        runs, a = [], 0
+        for m in range(1, B + 1):
+            if m == B or gs[m] != gs[a]:
+                runs.append((a, m))
+                a = m
+        reqs = [(torch.cat([text_emb[a:b], text_emb[B + a:B + b]]), lengths[a:b]) for a, b in runs]
+        lat0 = None if init_latents is None else [init_latents[a:b] for a, b in runs]
+        outs = self.sample_many(reqs, lat0, guidance=[gs[a] for a, _ in runs], **noise_kw)
+        joints = outs[0][0].new_zeros(B, max(int(x) for x in lengths), self.njoints, 3)
+        for (a, b), o in zip(runs, outs):
+            joints[a:b, :o[0].shape[1]] = o[0]
+        return joints
 
     @torch.no_grad()
     def gen_from_latent(self, batch):
@@ -447,12 +505,13 @@ class MLD(nn.Module):
         return remove_padding(joints.cpu(), length), remove_padding(joints_ref.cpu(), length)
 
     @torch.no_grad()
-    def edit(self, batch, strength: float, init_latents: Optional[torch.Tensor] = None, seed: Optional[int] = None, sample_mean: bool = True):
+    def edit(self, batch, strength: float, init_latents: Optional[torch.Tensor] = None, seed: Optional[int] = None, sample_mean: bool = True,
+             guidance_scale: Optional[float] = None):
         """Motion-to-motion under a new prompt, as diffusers' image-to-image pipelines do it: batch {"motion" [B, T, nfeats], "text", "length"} ->
         joints per motion (as ``forward`` returns them).  The motion is encoded (``HipMldVae.encode``; the distribution's mean, or its sample with
         ``sample_mean=False``), noised to scheduler step ``first_step = n - min(int(n * strength), n)`` with ``init_latents`` (default: torch.randn) and
         denoised from there under batch["text"] in ONE mldhip_sample_many_from call: strength 1 runs every step, strength 0.3 the last 30 % of them,
-        strength 0 (first_step == n) returns the reconstruction without a loop."""
+        strength 0 (first_step == n) returns the reconstruction without a loop.  ``guidance_scale``: passed on to ``sample``."""
         if not self.fused or self.vae_type == "no" or self.condition == "action":
             raise NotImplementedError("edit serves the fused text-to-motion latent model")
         motion, texts, lengths = batch["motion"], list(batch["text"]), [int(x) for x in batch["length"]]
@@ -467,6 +526,8 @@ class MLD(nn.Module):
             texts = [""] * len(texts) + ([""] * len(texts) if self.condition == "text_uncond" else texts)
         text_emb = self.text_encoder(texts).to(src.device)
         noise_kw = {} if self.eta == 0.0 else {"seed": seed}
+        if guidance_scale is not None:
+            noise_kw["guidance_scale"] = float(guidance_scale)
         joints, _, _ = self.sample(text_emb, lengths, init_latents, src_latents=src, first_step=first_step, **noise_kw)
         return remove_padding(joints.detach().cpu(), lengths)
 
