@@ -223,6 +223,9 @@ int mldhip_finalize_weights(mldhip_handle* h, void* stream);
  *   "fused_min_batch" auto picks the persistent loop from this many motions per call up; 0 (default) = by operand format, from the measured
  *                     crossover table (tools/ab_crossover.py, profiles/r04_loop_crossover.json): 192 on split-f16 MFMAs (19 ms per call
  *                     whatever the batch; the split-f16 latency kernels take 19.0 ms at 192 motions), 1 280 on exact-fp32 MFMAs (73 ms)
+ *   "loop_lean"       persistent loop ("loop_kernel" 3 / auto), both operand formats, every entry point: 1 (default) = the LAST denoiser layer of a step works
+ *                     on the latent token's rows only -- nothing behind it reads the time and condition rows -- except in its K and V products, which the
+ *                     latent query attends to (kernels/loop_fused.hpp `full`; latents equal to the bit); 0 = all three tokens in every layer
  *   "fused_x3"        F16X3 mode: 1 (default) = the persistent loop multiplies on split-f16 MFMAs (row-swizzled operand images, 4 weight
  *                     items in flight per lane: the settled forms of round 3's "fused_swz" / "fused_ring" knobs), 0 = on exact-fp32 MFMAs
  *   "cluster_inject"  (hooks build only) fault injection: 1 + the index of a cluster member that never raises its first flag (the wait bound shrinks to 2 ms): the members

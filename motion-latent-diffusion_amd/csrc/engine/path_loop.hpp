@@ -300,6 +300,7 @@ void launch_fused_loop(Ctx& c, const float* init_lat, int B, int n, float guidan
   a.lat = e->lat; a.skip = e->FS; a.ddim = e->loop_ddim; a.B = B; a.L = e->cfg.num_layers; a.n = n;
   a.guidance = guidance; a.init_sigma = 1.0f;
   a.traj = traj_table(e);
+  a.lean = e->loop_lean;
   const dim3 grid((B + 7) / 8);
   if (e->from_on) {                     // mldhip_sample_many_from: the from-forms on the context's start table, with or without noise
     a.starts = e->starts_dev;

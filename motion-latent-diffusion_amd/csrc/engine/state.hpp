@@ -174,6 +174,7 @@ struct mldhip_engine {
   int cluster_wt = 0;        // "cluster_wt": 0 (default) = a cluster whose twelve members report one XCC id stores its payloads plain (served by the shared L2; -3.5 % per call), any other cluster write-through; 1 = write-through (sc1) always
   int fused_x3 = 1;          // "fused_x3": in the split precision mode the sample-major loop multiplies on split-f16 MFMAs (0: exact fp32 MFMAs)
   int fused_dbg = 0;         // "fused_dbg": 5 = the split-mode loop with its phase counters (same arithmetic, mldhip_profile_trace "den_loop_phases"); 0 = off
+  int loop_lean = 1;         // "loop_lean": the sample-major loop's last layer works on the latent token's row tile only, except in its K and V products (loop_fused.hpp `full`: nothing behind that layer reads the time and condition rows); bit-identical latents.  0 = all three tiles everywhere
   int fused_min_batch = 0;   // "fused_min_batch": auto picks the sample-major loop from this many motions per call up; 0 = by operand format (320 split-f16, 1 280 fp32)
   int strip_min_rows = 768;  // "strip_min_rows": auto switches to the throughput kernels at 6B >= this many token rows
   int flash_attn = 1;        // "flash_attn": split-f16 frame-level self-attention key-blocked (attention.hpp attn_flash_x3_kernel): 0 never, 1 auto (>= 512 (sample, head) pairs), 2 always

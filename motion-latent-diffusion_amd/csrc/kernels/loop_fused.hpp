@@ -76,6 +76,7 @@ struct LoopArgs {
   const NoiseKey* keys = nullptr;        // ... [B] noise key per motion of the call
   const TrajRow* traj = nullptr;         // mldhip_sample_many_traj: [B] trajectory entry per motion of the call, or NULL (no trajectory: nothing is stored)
   const StartRow* starts = nullptr;      // den_loop_kernel<X3, kLoopFrom / kLoopFromEta>: [B] start entry per motion of the call
+  int lean = 0;                          // "loop_lean": 1 = the last layer works on the latent token's row tile only, except in its K and V products (see `full` in the kernel)
 };
 
 // den_loop_kernel<X3, kLoopEta>: the stochastic-DDIM form (eta > 0, include/mldhip.h "Noise contract") of the production loop.  It takes a value of
@@ -213,15 +214,55 @@ __global__ __launch_bounds__(512, 2) void den_loop_kernel(LoopArgs p) {
   // item's matrix instructions stay in front of it.  Pinned skip linears: 194 registers, NO scratch.  (Pinning every item is level; pinning
   // the nine GELU slices of mma_item_sliced into their slots -- hipcc collects them behind one matrix instruction -- gives the intended
   // 1 MFMA : 4 VALU interleave in the machine code and is 2 % SLOWER: the feed-forward phase is not an issue-order effect.)
+  // "loop_lean": behind the LAST layer only the latent token's rows (row tile 0) are read -- encoder.norm, CFG, DDIM -- and a row meets the other two tokens
+  // in the attention alone: that layer needs K and V of all three tiles and everything else of tile 0 only.  `nt` is the layer's tile count (3, or 1 in the lean
+  // layer), set at the top of a layer.  The layers share ONE body, so the work of tiles 1 and 2 sits behind wave-uniform scalar branches: matrix instructions ignore
+  // EXEC, and a second copy of the body (or of an item) would be a second copy of its matrix instructions.  Every branch tests its OWN opaque copy of nt: conditions
+  // the compiler can relate are threaded or unswitched (the head-pair and hidden-block loops are invariant in nt) into exactly such copies.  The eight full
+  // layers pay for every branch (a scalar move, compare and jump, and a scheduling region cut in two): the full path is the fall-through, a plain item has one
+  // branch, and the fragment reads of tiles 1 and 2 of the NEXT chunk sit inside the branch of the chunk's first item instead of behind one of their own.
+  int nt = 3;
+  auto full = [&]() __attribute__((always_inline)) {
+    int f = nt;
+#if !defined(MLDHIP_SIM)
+    asm volatile("" : "+s"(f));
+#endif
+    return f > 1;
+  };
+#define LF_FULL __builtin_expect(full(), 1)   /* (the hint has to stand in the `if` itself: it is lowered before the lambda is inlined) */
+  // the s-th split product of an item on row tile t (each tile keeps its own order: wh x_lo, wl x_hi, wh x_hi); fp32: k-slot s of 8
+  auto prod = [&](int s, int t, const U4& wh, const U4& wl, const F4 (&x)[3][2], f32x4 (&acc)[3]) __attribute__((always_inline)) {
+    if (t < kLfMmaTiles) acc[t] = mfma_x3_16x16x32(s == 1 ? wl : wh, __builtin_bit_cast(U4, x[t][s == 0 ? 1 : 0]), acc[t]);
+  };
+  auto prod32 = [&](int s, int t, const F4& y0, const F4& y1, const F4 (&x)[3][2], f32x4 (&acc)[3]) __attribute__((always_inline)) {
+    acc[t] = mfma_f32_16x16x4(s < 4 ? (&y0.x)[s] : (&y1.x)[s - 4], s < 4 ? (&x[t][0].x)[s] : (&x[t][1].x)[s - 4], acc[t]);
+  };
   auto pin_acc = [](f32x4 (&a)[3]) __attribute__((always_inline)) {
 #if !defined(MLDHIP_SIM)
     asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]));
 #endif
   };
-  auto mma_item = [&](int j, const F4 (&x)[3][2], f32x4 (&acc)[3], bool pin = false) __attribute__((always_inline)) {
+  // `gate`: the item's tiles 1 and 2 are skipped in the lean layer (every item but the K and V items and the skip linears)
+  auto no12 = []() __attribute__((always_inline)) {};
+  auto mma_item = [&](int j, const F4 (&x)[3][2], f32x4 (&acc)[3], bool pin, bool gate, auto&& next12) __attribute__((always_inline)) {
     const int slot = j % kLoopRing;
     if constexpr (DBG == 2) {
       acc[0][0] += ring[slot][0].x + ring[slot][1].w + x[0][0].x;
+    } else if (gate) {
+      const U4 wh = __builtin_bit_cast(U4, ring[slot][0]), wl = __builtin_bit_cast(U4, ring[slot][1]);
+      const F4 y0 = ring[slot][0], y1 = ring[slot][1];
+      constexpr int ns = X3 ? 3 : 8;
+      // tile 0's products first, then ONE branch around those of tiles 1 and 2 (a branch behind each of tile 0's three instead -- the interleave of an ungated
+      // item -- costs the full layers 6.9 % of the loop against 2.8 %, profiles/loop_lean_ab.json); `next12`: the next chunk's fragment reads of tiles 1 and 2
+#pragma unroll
+      for (int s = 0; s < ns; ++s) { if constexpr (X3) prod(s, 0, wh, wl, x, acc); else prod32(s, 0, y0, y1, x, acc); }
+      if (LF_FULL) {
+        next12();
+#pragma unroll
+        for (int s = 0; s < ns; ++s)
+#pragma unroll
+          for (int t = 1; t < 3; ++t) { if constexpr (X3) prod(s, t, wh, wl, x, acc); else prod32(s, t, y0, y1, x, acc); }
+      }
     } else if constexpr (X3) {
       const U4 wh = __builtin_bit_cast(U4, ring[slot][0]), wl = __builtin_bit_cast(U4, ring[slot][1]);
 #pragma unroll
@@ -259,32 +300,48 @@ __global__ __launch_bounds__(512, 2) void den_loop_kernel(LoopArgs p) {
   // instruction there are three free issue slots, and an in-order wave fills them only if the next instructions in ITS stream are
   // not matrix instructions.  (r03 phase counters: the feed-forward phase took 14.2 ms of the loop's 29.8 where its matrix
   // instructions need 7.9 -- the compiler's own interleave left MFMA and GELU time adding up.)
-  auto mma_item_sliced = [&](int j, const F4 (&x)[3][2], f32x4 (&acc)[3], auto&& epi) __attribute__((always_inline)) {
+  // The item's tiles 1 and 2 are always gated (linear1 is the only user).  `epi_t0`: the slices belong to row tile 0 and run in the lean layer too; else they go
+  // with the matrix instructions of tiles 1 and 2, behind the same branches (one per split product: the slices keep their places between the matrix
+  // instructions, and a full layer issues exactly the sequence it always did).  `next12`: as in mma_item.
+  auto mma_item_sliced = [&](int j, const F4 (&x)[3][2], f32x4 (&acc)[3], bool epi_t0, auto&& epi, auto&& next12) __attribute__((always_inline)) {
     const int slot = j % kLoopRing;
     if constexpr (DBG == 2) {
       acc[0][0] += ring[slot][0].x + ring[slot][1].w + x[0][0].x;
+      if (epi_t0 || LF_FULL) {
 #pragma unroll
-      for (int k = 0; k < 9; ++k) epi(k);
+        for (int k = 0; k < 9; ++k) epi(k);
+      }
     } else if constexpr (X3) {
       const U4 wh = __builtin_bit_cast(U4, ring[slot][0]), wl = __builtin_bit_cast(U4, ring[slot][1]);
 #pragma unroll
-      for (int t = 0; t < 3; ++t) { if (t < kLfMmaTiles) acc[t] = mfma_x3_16x16x32(wh, __builtin_bit_cast(U4, x[t][1]), acc[t]); epi(t); sched_fence(); }
+      for (int s = 0; s < 3; ++s) {
+        prod(s, 0, wh, wl, x, acc);
+        if (epi_t0) { epi(3 * s); sched_fence(); }
+        if (LF_FULL) {
+          if (s == 0) next12();
+          if (!epi_t0) { epi(3 * s); sched_fence(); }
 #pragma unroll
-      for (int t = 0; t < 3; ++t) { if (t < kLfMmaTiles) acc[t] = mfma_x3_16x16x32(wl, __builtin_bit_cast(U4, x[t][0]), acc[t]); epi(3 + t); sched_fence(); }
-#pragma unroll
-      for (int t = 0; t < 3; ++t) { if (t < kLfMmaTiles) acc[t] = mfma_x3_16x16x32(wh, __builtin_bit_cast(U4, x[t][0]), acc[t]); epi(6 + t); sched_fence(); }
+          for (int t = 1; t < 3; ++t) { prod(s, t, wh, wl, x, acc); epi(3 * s + t); sched_fence(); }
+        } else if (epi_t0) {
+          epi(3 * s + 1);
+          epi(3 * s + 2);
+        }
+      }
     } else {
       const F4 y0 = ring[slot][0], y1 = ring[slot][1];
-      const float yv[8] = {y0.x, y0.y, y0.z, y0.w, y1.x, y1.y, y1.z, y1.w};
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
-        const float xs[3] = {q < 4 ? (&x[0][0].x)[q] : (&x[0][1].x)[q - 4], q < 4 ? (&x[1][0].x)[q] : (&x[1][1].x)[q - 4], q < 4 ? (&x[2][0].x)[q] : (&x[2][1].x)[q - 4]};
-#pragma unroll
-        for (int t = 0; t < 3; ++t) acc[t] = mfma_f32_16x16x4(yv[q], xs[t], acc[t]);
-        epi(q);
+        prod32(q, 0, y0, y1, x, acc);
+        if (LF_FULL) {
+          if (q == 0) next12();
+          prod32(q, 1, y0, y1, x, acc);
+          prod32(q, 2, y0, y1, x, acc);
+          if (!epi_t0) epi(q);
+        }
+        if (epi_t0) epi(q);
         sched_fence();
       }
-      epi(8);
+      if (epi_t0 || LF_FULL) epi(8);
     }
     if constexpr (DBG != 1 && !(LF_EXP & 8)) gload(slot);
     sched_fence();
@@ -292,18 +349,27 @@ __global__ __launch_bounds__(512, 2) void den_loop_kernel(LoopArgs p) {
   // A group: 8 chunks of A (row r of tile 0 at a0 + 4g, next tile 16 * kLfXs words on, chunk c at + 32 c) against NP column
   // blocks whose items alternate in the stream (chunk-major): one read of the A fragments feeds NP items.
   // (the A fragments of chunk c + 1 are requested before chunk c is multiplied: the fence in mma_item keeps that order)
-  auto afrag = [&](const float* a0, int ts, int c, F4 (&x)[3][2]) __attribute__((always_inline)) {
+  // (`gate`: tile 0's fragments only; those of tiles 1 and 2 are read by afrag12 from inside an item's branch -- in the lean layer nobody wrote those rows)
+  auto afrag = [&](const float* a0, int ts, int c, F4 (&x)[3][2], bool gate = false) __attribute__((always_inline)) {
+    x[0][0] = ld4(a0 + 32 * c); x[0][1] = ld4(a0 + 32 * c + 16);
+    if (!gate) {
 #pragma unroll
-    for (int t = 0; t < kLfMmaTiles; ++t) { x[t][0] = ld4(a0 + t * ts + 32 * c); x[t][1] = ld4(a0 + t * ts + 32 * c + 16); }
+      for (int t = 1; t < kLfMmaTiles; ++t) { x[t][0] = ld4(a0 + t * ts + 32 * c); x[t][1] = ld4(a0 + t * ts + 32 * c + 16); }
+    }
   };
-  auto run2 = [&](const float* a0, f32x4 (&acc0)[3], f32x4 (&acc1)[3], bool pin = false) __attribute__((always_inline)) {
+  auto afrag12 = [&](const float* a0, int ts, int c, F4 (&x)[3][2]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int t = 1; t < kLfMmaTiles; ++t) { x[t][0] = ld4(a0 + t * ts + 32 * c); x[t][1] = ld4(a0 + t * ts + 32 * c + 16); }
+  };
+  auto run2 = [&](const float* a0, f32x4 (&acc0)[3], f32x4 (&acc1)[3], bool pin = false, bool gate = false) __attribute__((always_inline)) {
     F4 x[2][3][2];
-    afrag(a0, 16 * kLfXs, 0, x[0]);
+    afrag(a0, 16 * kLfXs, 0, x[0], gate);
+    if (gate && LF_FULL) afrag12(a0, 16 * kLfXs, 0, x[0]);
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
-      if (c + 1 < 8) afrag(a0, 16 * kLfXs, c + 1, x[(c + 1) & 1]);
-      mma_item(2 * c, x[c & 1], acc0, pin);
-      mma_item(2 * c + 1, x[c & 1], acc1, pin);
+      if (c + 1 < 8) afrag(a0, 16 * kLfXs, c + 1, x[(c + 1) & 1], gate);
+      mma_item(2 * c, x[c & 1], acc0, pin, gate, [&]() __attribute__((always_inline)) { if (c + 1 < 8) afrag12(a0, 16 * kLfXs, c + 1, x[(c + 1) & 1]); });
+      mma_item(2 * c + 1, x[c & 1], acc1, pin, gate, no12);
     }
   };
   auto run3 = [&](const float* a0, f32x4 (&acc0)[3], f32x4 (&acc1)[3], f32x4 (&acc2)[3]) __attribute__((always_inline)) {
@@ -312,30 +378,33 @@ __global__ __launch_bounds__(512, 2) void den_loop_kernel(LoopArgs p) {
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
       if (c + 1 < 8) afrag(a0, 16 * kLfXs, c + 1, x[(c + 1) & 1]);
-      mma_item(3 * c, x[c & 1], acc0);
-      mma_item(3 * c + 1, x[c & 1], acc1);
-      mma_item(3 * c + 2, x[c & 1], acc2);
+      mma_item(3 * c, x[c & 1], acc0, false, true, no12);       // Q: of the latent token only in the lean layer; K and V of all three tokens always
+      mma_item(3 * c + 1, x[c & 1], acc1, false, false, no12);
+      mma_item(3 * c + 2, x[c & 1], acc2, false, false, no12);
     }
   };
-  // one column block against 8 chunks (linear1 of one 128-wide hidden block)
+  // one column block against 8 chunks (linear1 of one 128-wide hidden block; gated)
   auto run1 = [&](const float* a0, f32x4 (&acc0)[3]) __attribute__((always_inline)) {
     F4 x[2][3][2];
-    afrag(a0, 16 * kLfXs, 0, x[0]);
+    afrag(a0, 16 * kLfXs, 0, x[0], true);
+    if (LF_FULL) afrag12(a0, 16 * kLfXs, 0, x[0]);
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
-      if (c + 1 < 8) afrag(a0, 16 * kLfXs, c + 1, x[(c + 1) & 1]);
-      mma_item(c, x[c & 1], acc0);
+      if (c + 1 < 8) afrag(a0, 16 * kLfXs, c + 1, x[(c + 1) & 1], true);
+      mma_item(c, x[c & 1], acc0, false, true, [&]() __attribute__((always_inline)) { if (c + 1 < 8) afrag12(a0, 16 * kLfXs, c + 1, x[(c + 1) & 1]); });
     }
   };
-  // both column blocks of linear2 against the 4 chunks of one hidden block (row stride kLfHs)
+  // both column blocks of linear2 against the 4 chunks of one hidden block (row stride kLfHs; gated)
   auto run2h = [&](const float* a0, f32x4 (&acc0)[3], f32x4 (&acc1)[3]) __attribute__((always_inline)) {
     F4 x[2][3][2];
-    afrag(a0, 16 * kLfHs, 0, x[0]);
+    afrag(a0, 16 * kLfHs, 0, x[0], true);
+    if (LF_FULL) afrag12(a0, 16 * kLfHs, 0, x[0]);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      if (c + 1 < 4 && (!(LF_EXP & 4) || c == 0)) afrag(a0, 16 * kLfHs, c + 1, x[(c + 1) & 1]);
-      mma_item(2 * c, x[c & 1], acc0);
-      mma_item(2 * c + 1, x[c & 1], acc1);
+      const bool rd = c + 1 < 4 && (!(LF_EXP & 4) || c == 0);
+      if (rd) afrag(a0, 16 * kLfHs, c + 1, x[(c + 1) & 1], true);
+      mma_item(2 * c, x[c & 1], acc0, false, true, [&]() __attribute__((always_inline)) { if (rd) afrag12(a0, 16 * kLfHs, c + 1, x[(c + 1) & 1]); });
+      mma_item(2 * c + 1, x[c & 1], acc1, false, true, no12);
     }
   };
   // a copy of a lane-dependent index the optimiser cannot see through: address arithmetic built on it stays where it is written
@@ -370,27 +439,35 @@ __global__ __launch_bounds__(512, 2) void den_loop_kernel(LoopArgs p) {
       st4(row + cq0, F4{v[0], v[1], v[2], v[3]});
     }
   };
-  auto put = [&](float* buf, int st, int cw, const float (&val)[3][4]) __attribute__((always_inline)) {
+  auto put = [&](float* buf, int st, int cw, const float (&val)[3][4], int ntl = 3) __attribute__((always_inline)) {
 #pragma unroll
-    for (int t = 0; t < 3; ++t) put_row(buf, st, cw, t, val[t]);
+    for (int t = 0; t < 3; ++t)
+      if (t < ntl) put_row(buf, st, cw, t, val[t]);
   };
   // ... and back: the residual of a LayerNorm is read from the operand buffer it was multiplied from (split mode: high + low
   // half, the value the GEMMs saw, 2^-22 from the fp32 one), so no activation stays in registers across a GEMM phase
-  auto get = [&](const float* buf, int st, int cw, float (&val)[3][4]) __attribute__((always_inline)) {
+  auto get_row = [&](const float* buf, int st, int cw, int t, float (&val)[4]) __attribute__((always_inline)) {
+    const float* row = buf + (t * 16 + r) * st + cw;
+    if constexpr (X3) {
+      const unsigned* w = reinterpret_cast<const unsigned*>(row) + rw0;
+      const U2 h = *reinterpret_cast<const U2*>(w), l = *reinterpret_cast<const U2*>(w + 16);
+      val[0] = f16_bits_value(h.x) + f16_bits_value(l.x);
+      val[1] = f16_bits_value(h.x >> 16) + f16_bits_value(l.x >> 16);
+      val[2] = f16_bits_value(h.y) + f16_bits_value(l.y);
+      val[3] = f16_bits_value(h.y >> 16) + f16_bits_value(l.y >> 16);
+    } else {
+      const F4 v = ld4(row + cq0);
+      val[0] = v.x; val[1] = v.y; val[2] = v.z; val[3] = v.w;
+    }
+  };
+  // the residual rows of tile t of both column blocks of Xs + a GEMM's accumulators + its bias: the input of a LayerNorm
+  auto resid = [&](float (&v)[2][3][4], const f32x4 (&a0)[3], const f32x4 (&a1)[3], const float (&b0)[4], const float (&b1)[4], int t) __attribute__((always_inline)) {
+    get_row(Xs, kLfXs, 0, t, v[0][t]);
+    get_row(Xs, kLfXs, 128, t, v[1][t]);
 #pragma unroll
-    for (int t = 0; t < 3; ++t) {
-      const float* row = buf + (t * 16 + r) * st + cw;
-      if constexpr (X3) {
-        const unsigned* w = reinterpret_cast<const unsigned*>(row) + rw0;
-        const U2 h = *reinterpret_cast<const U2*>(w), l = *reinterpret_cast<const U2*>(w + 16);
-        val[t][0] = f16_bits_value(h.x) + f16_bits_value(l.x);
-        val[t][1] = f16_bits_value(h.x >> 16) + f16_bits_value(l.x >> 16);
-        val[t][2] = f16_bits_value(h.y) + f16_bits_value(l.y);
-        val[t][3] = f16_bits_value(h.y >> 16) + f16_bits_value(l.y >> 16);
-      } else {
-        const F4 v = ld4(row + cq0);
-        val[t][0] = v.x; val[t][1] = v.y; val[t][2] = v.z; val[t][3] = v.w;
-      }
+    for (int i = 0; i < 4; ++i) {
+      v[0][t][i] += a0[t][i] + b0[i];
+      v[1][t][i] += a1[t][i] + b1[i];
     }
   };
 
@@ -533,6 +610,7 @@ __global__ __launch_bounds__(512, 2) void den_loop_kernel(LoopArgs p) {
     for (int l = 0; l < p.L; ++l) {
       float x[2][3][4];                            // norm2 output of this layer at this lane's positions (dies inside the layer: the next one reads Xs)
       const float* sm = prm + pbuf * kLfPrmFloats;        // this layer's small parameters (LDS)
+      nt = (p.lean && l == p.L - 1) ? 1 : 3;              // row tiles this layer works on outside its K and V products (see `full`)
       // ================= self-attention: two heads at a time (cross_attention.py:265-266; nn.MultiheadAttention, 4 heads of 64)
       for (int hp = 0; hp < 2; ++hp) {
         f32x4 q[3], k[3], vv[3];
@@ -548,10 +626,12 @@ __global__ __launch_bounds__(512, 2) void den_loop_kernel(LoopArgs p) {
 #pragma unroll
           for (int i = 0; i < 4; ++i) { q[t][i] += bqv[i]; k[t][i] += bkv[i]; vv[t][i] += bvv[i]; }
         float* sw = sc + hp * 1152 + (wave >> 2) * 576 + r * 4 + (wave & 3);      // (one exchange buffer per head pair: no barrier between the pairs)
+        const int nta = LF_FULL ? 3 : 1;      // query tiles of this head pair: the latent token's only in the lean layer (its row of As is the only one written)
 #pragma unroll
         for (int t = 0; t < 3; ++t)
 #pragma unroll
           for (int u = 0; u < 3; ++u) {
+            if (t >= nta) continue;
             float sp = (q[t][0] * k[u][0] + q[t][1] * k[u][1]) + (q[t][2] * k[u][2] + q[t][3] * k[u][3]);
             sp = sum_groups(sp);
             if (g == 0) sw[(t * 3 + u) * 64] = sp;
@@ -561,6 +641,7 @@ __global__ __launch_bounds__(512, 2) void den_loop_kernel(LoopArgs p) {
         float o[3][4];
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
+          if (t >= nta) continue;
           float a[3];
 #pragma unroll
           for (int u = 0; u < 3; ++u) {
@@ -574,7 +655,7 @@ __global__ __launch_bounds__(512, 2) void den_loop_kernel(LoopArgs p) {
 #pragma unroll
           for (int i = 0; i < 4; ++i) o[t][i] = p0 * vv[0][i] + p1 * vv[1][i] + p2 * vv[2][i];
         }
-        put(As, kLfXs, hp * 128, o);
+        put(As, kLfXs, hp * 128, o, nta);
         if (hp == 1) __syncthreads();       // the attention output is complete before anybody multiplies it (r04: `sc` is double buffered by head pair,
                                             // so the pairs need no barrier between them: 18.94 -> 18.83 ms at 1 280 motions)
         stamp(1);
@@ -584,26 +665,22 @@ __global__ __launch_bounds__(512, 2) void den_loop_kernel(LoopArgs p) {
         f32x4 o0[3], o1[3];
         zero3(o0); zero3(o1);
         prm_fetch(l + 1 < p.L ? l + 1 : 0);
-        run2(aa, o0, o1);
+        run2(aa, o0, o1, false, true);
         prm_store(pbuf ^ 1);
         stamp(2);
         const F4 ob0 = ld4(sm + kLsOutB + cq0), ob1 = ld4(sm + kLsOutB + 128 + cq0);
         const float ob0v[4] = {ob0.x, ob0.y, ob0.z, ob0.w}, ob1v[4] = {ob1.x, ob1.y, ob1.z, ob1.w};
+        const int ntn = LF_FULL ? 3 : 1;
         float u[2][3][4];
-        get(Xs, kLfXs, 0, u[0]);
-        get(Xs, kLfXs, 128, u[1]);
+        // (the residual rows themselves are read and added on all three tiles in the lean layer too -- rows 16 .. 47 of Xs still hold the layer's input there: a branch
+        // around these four reads and 48 additions costs 14 registers, 234 against 220, and the norm below drops the two tiles anyway)
 #pragma unroll
-        for (int t = 0; t < 3; ++t)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            u[0][t][i] += o0[t][i] + ob0v[i];
-            u[1][t][i] += o1[t][i] + ob1v[i];
-          }
-        ln_part1(u, 3);
+        for (int t = 0; t < 3; ++t) resid(u, o0, o1, ob0v, ob1v, t);
+        ln_part1(u, ntn);
         __syncthreads();
-        ln_part2(u, 3, sm + kLsN1W, sm + kLsN1B);
-        put(Xs, kLfXs, 0, u[0]);
-        put(Xs, kLfXs, 128, u[1]);
+        ln_part2(u, ntn, sm + kLsN1W, sm + kLsN1B);
+        put(Xs, kLfXs, 0, u[0], ntn);
+        put(Xs, kLfXs, 128, u[1], ntn);
         __syncthreads();
         stamp(3);
       }
@@ -624,7 +701,7 @@ __global__ __launch_bounds__(512, 2) void den_loop_kernel(LoopArgs p) {
           // split) per item over the first six items, in nine slices of two to five instructions (mma_item_sliced); the tile's two
           // 8-byte stores go out with the odd items
           F4 x[2][3][2];
-          if (more) afrag(xa, 16 * kLfXs, 0, x[0]);
+          if (more) { afrag(xa, 16 * kLfXs, 0, x[0], true); if (LF_FULL) afrag12(xa, 16 * kLfXs, 0, x[0]); }
           unsigned ph = 0, pl = 0, qh = 0, ql = 0;
           float f0 = 0.f, f1 = 0.f;
           float u0 = 0.f, u1 = 0.f, hh0 = 0.f, hh1 = 0.f, tt0 = 0.f, tt1 = 0.f, ee0 = 0.f, ee1 = 0.f, pp0 = 0.f, pp1 = 0.f;
@@ -686,10 +763,14 @@ __global__ __launch_bounds__(512, 2) void den_loop_kernel(LoopArgs p) {
                 }
               }
             };
+            // (the slices of items 0 and 1 are row tile 0's; those of items 2 .. 5 are of tiles 1 and 2: not in the lean layer)
             if (more) {
-              if (c + 1 < 8 && (!(LF_EXP & 1) || c == 0)) afrag(xa, 16 * kLfXs, c + 1, x[(c + 1) & 1]);
-              mma_item_sliced(c, x[c & 1], nxt, epi);
-            } else {
+              const bool rd = c + 1 < 8 && (!(LF_EXP & 1) || c == 0);
+              if (rd) afrag(xa, 16 * kLfXs, c + 1, x[(c + 1) & 1], true);
+              auto next12 = [&]() __attribute__((always_inline)) { if (rd) afrag12(xa, 16 * kLfXs, c + 1, x[(c + 1) & 1]); };
+              if (c >= 6 && DBG != 4) mma_item(c, x[c & 1], nxt, false, true, next12);      // (no slices left: a plain item, one branch)
+              else mma_item_sliced(c, x[c & 1], nxt, c < 2, epi, next12);
+            } else if (c < 2 || (c < 6 && LF_FULL)) {
 #pragma unroll
               for (int k = 0; k < 9; ++k) epi(k);
             }
@@ -707,18 +788,12 @@ __global__ __launch_bounds__(512, 2) void den_loop_kernel(LoopArgs p) {
         stamp(4);
         const F4 lb0 = ld4(sm + kLsL2B + cq0), lb1 = ld4(sm + kLsL2B + 128 + cq0);
         const float lb0v[4] = {lb0.x, lb0.y, lb0.z, lb0.w}, lb1v[4] = {lb1.x, lb1.y, lb1.z, lb1.w};
-        get(Xs, kLfXs, 0, x[0]);
-        get(Xs, kLfXs, 128, x[1]);
+        const int ntn = LF_FULL ? 3 : 1;
 #pragma unroll
-        for (int t = 0; t < 3; ++t)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            x[0][t][i] += y0[t][i] + lb0v[i];
-            x[1][t][i] += y1[t][i] + lb1v[i];
-          }
-        ln_part1(x, 3);
+        for (int t = 0; t < 3; ++t) resid(x, y0, y1, lb0v, lb1v, t);     // (all three tiles, as before norm1)
+        ln_part1(x, ntn);
         __syncthreads();
-        ln_part2(x, 3, sm + kLsN2W, sm + kLsN2B);
+        ln_part2(x, ntn, sm + kLsN2W, sm + kLsN2B);
         stamp(7);
       }
       if (l + 1 < p.L) {
@@ -861,5 +936,7 @@ __global__ __launch_bounds__(512, 2) void den_loop_kernel(LoopArgs p) {
     }
   }
 }
+
+#undef LF_FULL
 
 }  // namespace mld

@@ -200,6 +200,9 @@ int mldhip_set_option(mldhip_handle* e, const char* name, int64_t value) {
     if (value < 0 || value > 2) return e->fail(MLDHIP_EINVAL, "range_probe must be 0 (off), 1 (seeded probe batch at finalize) or 2 (1 + the reverse-loop probe again on the caller's first batch)");
     e->range_probe = (int)value;
     e->finalized = false;            // the probe is part of finalize
+  } else if (n == "loop_lean") {
+    if (value != 0 && value != 1) return e->fail(MLDHIP_EINVAL, "loop_lean must be 0 or 1");
+    e->loop_lean = (int)value;
   } else if (n == "fused_min_batch") {
     if (value < 0) return e->fail(MLDHIP_EINVAL, "fused_min_batch must be >= 0 (0 = automatic)");
     e->fused_min_batch = (int)std::min<int64_t>(value, 1 << 30);

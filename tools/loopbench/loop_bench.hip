@@ -3,7 +3,7 @@
 // one hipcc + one gpurun call:
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I motion-latent-diffusion_amd/csrc/kernels [-DLB_VARIANT='true, 0'] [-D...] \
 //         -o gpurun_out/lb_x tools/loopbench/loop_bench.hip
-//   gpurun -- 'gpurun_out/lb_x [motions=2048] [reps=5] [trace=0|1]'
+//   lb_x [motions=2048] [reps=5] [trace=0|1] [lean=1|0]          (on the MI355X)
 // Prints one JSON line: ms per launch (min / median), and with trace=1 the kernel's own phase counters (the DBG 5 build of the same
 // variant flags: LB_TRACE_VARIANT).  Timing only -- results are checked through the library (tests/, simulator + GPU), never here.
 #include <hip/hip_runtime.h>
@@ -12,6 +12,10 @@
 #include <cstdlib>
 #include <random>
 #include <vector>
+#include "attention.hpp"
+#include "elementwise.hpp"
+#include "gemm.hpp"
+#include "novae.hpp"        // latent_noise4 (the eta forms of the loop body name it), behind the headers it leans on, in mldhip.hip's order
 #include "loop_fused.hpp"
 
 #ifndef LB_VARIANT
@@ -25,7 +29,7 @@
 using namespace mld;
 
 int main(int argc, char** argv) {
-  const int B = argc > 1 ? atoi(argv[1]) : 2048, reps = argc > 2 ? atoi(argv[2]) : 5, trace = argc > 3 ? atoi(argv[3]) : 0;
+  const int B = argc > 1 ? atoi(argv[1]) : 2048, reps = argc > 2 ? atoi(argv[2]) : 5, trace = argc > 3 ? atoi(argv[3]) : 0, lean = argc > 4 ? atoi(argv[4]) : 1;
   const int L = 9, nb = 4, n = 50, ips = L * kLoopItemsLayer + nb * kLoopItemsSkip, nit = ips + 8;
   const int grid = (B + 7) / 8;
   std::mt19937 rng(1234);
@@ -72,7 +76,7 @@ int main(int argc, char** argv) {
   CK(hipMemset(tr, 0, 64 * 8 * 16 * sizeof(unsigned long long)));
   LoopArgs a;
   a.stream = stream; a.ips = ips; a.small = small; a.T1 = T1; a.TP = TP; a.init_lat = init; a.lat = lat; a.skip = skip; a.ddim = ddim;
-  a.B = B; a.L = L; a.n = n; a.guidance = 7.5f; a.init_sigma = 1.0f; a.trace = tr;
+  a.B = B; a.L = L; a.n = n; a.guidance = 7.5f; a.init_sigma = 1.0f; a.trace = tr; a.lean = lean;
   CK(hipFuncSetAttribute((const void*)den_loop_kernel<LB_VARIANT>, hipFuncAttributeMaxDynamicSharedMemorySize, kLoopLdsBytes));
   CK(hipFuncSetAttribute((const void*)den_loop_kernel<LB_TRACE_VARIANT>, hipFuncAttributeMaxDynamicSharedMemorySize, kLoopLdsBytes));
   hipEvent_t e0, e1;
@@ -90,7 +94,7 @@ int main(int argc, char** argv) {
   std::vector<float> hl(256);
   CK(hipMemcpy(hl.data(), lat, 256 * sizeof(float), hipMemcpyDeviceToHost));
   double cs = 0; for (float v : hl) cs += v;
-  printf("{\"variant\": \"%s\", \"motions\": %d, \"ms_min\": %.3f, \"ms_med\": %.3f, \"lat_checksum\": %.6g", LB_NAME, B, ms.front(), ms[ms.size() / 2], cs);
+  printf("{\"variant\": \"%s\", \"motions\": %d, \"lean\": %d, \"ms_min\": %.3f, \"ms_med\": %.3f, \"lat_checksum\": %.6g", LB_NAME, B, lean, ms.front(), ms[ms.size() / 2], cs);
   if (trace) {
     hipLaunchKernelGGL((den_loop_kernel<LB_TRACE_VARIANT>), dim3(grid), dim3(512), kLoopLdsBytes, 0, a);
     CK(hipDeviceSynchronize());
