@@ -18,6 +18,9 @@
  *   - work is enqueued on the caller's `stream` (a hipStream_t passed as void*, NULL = the null
  *     stream) and is stream-ordered: no implicit device synchronisation.
  *   - the caller owns every I/O buffer; the engine owns weights, workspaces and the captured hipGraphs.
+ *   - the request, key, start, guidance and trajectory tables of a call are read on the host before it returns.  actions_host and lengths_host are
+ *     handed to hipMemcpyAsync as they are: in pageable memory they are consumed when the call returns (the runtime stages or completes such a copy
+ *     before it returns); in page-locked memory (hipHostMalloc, hipHostRegister) they must stay unchanged until the stream has passed the call.
  *   - one handle per device and model variant; a handle is not thread-safe (issue its calls from one host thread).
  *     Calls on DIFFERENT streams overlap on the GPU when the handle was created with max_in_flight > 1.
  */
@@ -91,7 +94,9 @@ enum {                     /* arithmetic mode of the matrix kernels.  In EVERY m
  *   - guidance_scale <= 1 runs the same kernels with guidance 1.0 (the conditional half of the [2B] batch, which the entry points still take); on an
  *     action engine mldhip_denoiser_forward_action then gives no row the zero embedding.
  * All of them compute the same model.  The whole accepted envelope is tested against a float64 reference, on the MI355X and on the functional simulator
- * (tests/test_gpu_config_envelope.py, tests/test_config_envelope_sim.py; measured errors in profiles/config_envelope.json). */
+ * (tests/test_gpu_config_envelope.py, tests/test_config_envelope_sim.py; measured errors in profiles/config_envelope.json); the action-conditioned
+ * models on every loop family, serving entry and ActorVae frame length in tests/test_gpu_action_edges.py and tests/test_action_edges_sim.py
+ * (profiles/action_edges.json). */
 typedef struct mldhip_config {
   int32_t struct_size;          /* sizeof(mldhip_config), for ABI evolution */
   int32_t latent_dim;           /* model.latent_dim[1]  = 256 */
