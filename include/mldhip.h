@@ -153,6 +153,11 @@ typedef struct mldhip_config {
   int32_t t2m_max_motions;      /* capacity: motions per mldhip_t2m_motion_embed call and captions per mldhip_t2m_text_embed call; 0 (default) = 2 x max_batch
                                  * (a batch's generated and ground-truth motions in one call) */
   int32_t t2m_max_words;        /* capacity: words per caption (L of mldhip_t2m_text_embed); 0 (default) = 32 */
+  /* ---- the optional SMPL body model (mldhip_smpl_forward below; MLDHIP_ABI_VERSION stays 8: callers detect the feature by the presence of the symbol).  Read only
+   * when struct_size covers it (a caller's struct that ends behind t2m_max_words means no body model).  With smpl_verts > 0 mldhip_create refuses nfeats != 150;
+   * the field is otherwise independent of vae_arch / condition. */
+  int32_t smpl_verts;           /* 0 (default) = no body model: no weights, no workspace, every smpl.* key accepted and ignored, mis-shaped ones included;
+                                 * 1 .. 16384 = V, the vertex count of the body (SMPL: 6890) */
 } mldhip_config;
 
 enum { MLDHIP_COND_TEXT = 0, MLDHIP_COND_ACTION = 1 };
@@ -526,7 +531,7 @@ int mldhip_denoiser_forward(mldhip_handle* h, const float* sample_dev, int32_t t
  * (mld/models/modeltype/mld.py:716-735: cond = cat(zeros_like(actions), actions); _diffusion_reverse;
  * vae.decode) for an engine created with condition = MLDHIP_COND_ACTION.
  *   actions_host      [B] int32 class labels in [0, nclasses)
- *   feats_out_dev     [B, Tmax, nfeats]  (rot6d/xyz features; joints need SMPL, which is out of scope) */
+ *   feats_out_dev     [B, Tmax, nfeats]  (rot6d features; mldhip_smpl_forward below turns them into joints and vertices on a handle with smpl_verts > 0) */
 int mldhip_sample_action(mldhip_handle* h, const int32_t* actions_host, const float* init_latents_dev,
                          const int32_t* lengths_host, int32_t B, float* latents_out_dev, float* feats_out_dev,
                          void* stream);
@@ -658,6 +663,55 @@ int mldhip_t2m_motion_embed(mldhip_handle* h, const float* feats_dev /*[B,T,nfea
                             float* emb_out_dev /*[B,512]*/, void* stream);
 int mldhip_t2m_text_embed(mldhip_handle* h, const float* word_embs_dev /*[B,L,300]*/, const float* pos_ohot_dev /*[B,L,15]*/,
                           const int32_t* text_lengths_host, int32_t B, int32_t L, float* emb_out_dev /*[B,512]*/, void* stream);
+
+/* The SMPL body model (handles created with smpl_verts = V > 0).  Replaces: Rotation2xyz (mld/transforms/rotation2xyz.py:10-114) over smplx.SMPLLayer as the two
+ * lambdas of MLD.__init__ call it on the action path (mld/models/modeltype/mld.py:118-143: feats2joints_eval with jointstype 'smpl', feats2joints with
+ * jointstype 'vertices').  A restatement of the published SMPL / linear-blend-skinning algorithm.
+ *
+ * WEIGHTS.  One more optional all-or-nothing group, float32 (a wrong shape is MLDHIP_EINVAL, mldhip_missing_keys reports a half-loaded group; with
+ * smpl_verts = 0 every smpl.* key stays accepted and ignored, mis-shaped ones included):
+ *   smpl.v_template [V][3];  smpl.posedirs [207][3V], column 3 v + c (smplx's buffer: the file's [V][3][207] reshaped to [3V][207] and transposed);
+ *   smpl.J_regressor [24][V];  smpl.lbs_weights [V][24] (dense: rows need not be sparse);  smpl.parents [24], integers stored as float32, parents[0] = -1.
+ * Finalize refuses a parents[i] that is not an integer in [0, i) for i >= 1.  The SHAPE IS FIXED: v_shaped = v_template (the reference always passes betas = 0:
+ * rotation2xyz.py:74-79, beta = 0 at both call sites); a caller who wants a body shape adds shapedirs . betas to v_template on the host, which is exact because the
+ * joints are regressed from v_shaped.  The rest joints J = J_regressor v_template [24][3] are computed once at finalize.
+ *
+ * FEATURES (sample.view(..., 6, 25).permute(0, 3, 2, 1), mld.py:121,133).  Feature c 25 + j is component c (0 .. 5) of slot j; slots 0 .. 23 are the rot6d of the
+ * global orientation and the 23 body joints; slot 24, components 0 .. 2, is the translation.  Features are used as they are: no mean / std.
+ * rot6d -> matrix (pytorch3d's rotation_6d_to_matrix), a1 = components 0 .. 2, a2 = components 3 .. 5:
+ *   b1 = a1 / max(|a1|, 1e-12);  u = a2 - (b1 . a2) b1;  b2 = u / max(|u|, 1e-12);  b3 = b1 x b2;  R has ROWS b1, b2, b3.
+ * CHAIN AND SKINNING.  G_0 = [R_0 | J_0];  G_i = G_parent(i) . [R_i | J_i - J_parent(i)];  posed joint i = the translation of G_i;  A_i = [G_i.R | G_i.t - G_i.R J_i];
+ *   pose feature pf = flatten(R_1 - I, ..., R_23 - I) in joint, row, column order (207 values);  vp[v] = v_template[v] + sum_k pf[k] posedirs[k][3 v + c];
+ *   vert[v] = sum_j W[v][j] (A_j.R vp[v] + A_j.t).
+ *
+ * OUTPUTS AND THE PADDED-FRAME RULE.  trans[b][t] = slot 24 of frame t, read as it is, also from padded frames.
+ *   joints [B][T][24][3]: a valid frame (t < len) holds joint_j - joint_0, a padded frame 0; with MLDHIP_SMPL_TRANS_JOINTS (the reference's vertstrans = True)
+ *     trans[b][t] - trans[b][0] is added to EVERY frame, padded ones included -- what rotation2xyz.py:94-109 does: the mask is applied before the translation, so
+ *     zero-padded features give -trans[b][0] on padded frames;
+ *   vertices [B][T][V][3]: a valid frame holds vert (not root-centred), a padded frame 0; with MLDHIP_SMPL_TRANS_VERTS the same term is added to every frame (the
+ *     model's own call sites leave this off).
+ * Not served (mld_hip.smpl.HipSmpl.rot2xyz raises, naming each): the vertex-regressed joint sets 'a2m' / 'a2mpl' / 'vibe' (no call site in mld.py; they need
+ * J_regressor_extra.npy and smplx's vertex-id table), pose_rep other than 'rot6d', glob = False, betas.
+ *
+ * KERNELS (kernels/smpl.hpp).  The chain kernel: one lane per frame -- rot6d -> R, the 24-joint chain, the joints output, pf (K padded to 208 with a zero) and A
+ * (24 x 12 floats), laid out as the vertex kernel's matrix operands.  The vertex kernel (one launch: the [frames][3V] offsets never go to memory): 16 frames x 16
+ * vertices per MFMA tile; three accumulators take pf . posedirs (posedirs re-laid coordinate-planar per 16-vertex block at finalize), twelve more the blended matrix
+ * sum_j W[v][j] A_j as a [16 x 24] x [24 x 16] product per entry -- all fifteen in one lane layout, so the skinning of a (frame, vertex) is 12 FMAs in registers --
+ * then the store; a workgroup stages the pf / A tiles of 32 frames in LDS once and walks the vertex blocks.
+ * ARITHMETIC: exact-fp32 MFMAs (v_mfma_f32_16x16x4_f32) and fp32 VALU in EVERY precision mode -- no stage of the range contract; an MLDHIP_PREC_F16X3 handle gives
+ * the same bits as an MLDHIP_PREC_F32 one.  Reasoning (an ESTIMATE, see profiles/smpl_ab.json for what was measured): 8.6 MFLOP of blend products and 83 KB of
+ * output per frame, i.e. 33 GFLOP for HumanAct12's 64 x 60 frames = 0.2 ms at the fp32 matrix peak against a reverse loop of about 7 ms; and posedirs lives at
+ * 1e-3 .. 1e-2, where the low half of a split-f16 image is a half subnormal (see the range contract above).
+ *
+ * The call is stream-ordered and issued eagerly (no hipGraph); lengths reach the kernels through an engine-owned table uploaded with the call; non-finite output
+ * values are counted into the sticky counter of mldhip_numeric_status WHILE they are stored (no separate pass over the vertices).  verts_out_dev == NULL runs the
+ * chain kernel only; its joints are bit-identical to those of a call that also asks for vertices.  More than 4 096 frames are processed in chunks (workspace
+ * bound); a frame's numbers do not depend on the chunk, the tile or the batch it is in.
+ * MLDHIP_EINVAL: B outside 1 .. max_batch, T outside 1 .. max_frames, a length outside 1 .. T, both outputs NULL, unknown flag bits, a null input.
+ * MLDHIP_ESTATE: no body model on the handle, the group not loaded, the handle not finalized. */
+enum { MLDHIP_SMPL_TRANS_JOINTS = 1, MLDHIP_SMPL_TRANS_VERTS = 2 };
+int mldhip_smpl_forward(mldhip_handle* h, const float* feats_dev /*[B,T,150]*/, const int32_t* lengths_host, int32_t B, int32_t T,
+                        int32_t flags, float* joints_out_dev /*[B,T,24,3] or NULL*/, float* verts_out_dev /*[B,T,V,3] or NULL*/, void* stream);
 
 /* Replaces: HumanML3DDataModule.feats2joints (mld/data/HumanML3D.py:41-45 -> recover_from_ric,
  * mld/data/humanml/scripts/motion_process.py:415-432).  feats [B,T,nfeats] -> joints [B,T,njoints,3]. */

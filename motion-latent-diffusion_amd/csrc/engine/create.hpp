@@ -1,7 +1,7 @@
 // Handle construction and teardown: the cluster-lane lock of a device, config validation, the workspace carve of the two variants,
 // the dynamic-LDS registration list, create_engine / destroy_engine.
 // Part of libmldhip's single translation unit (included by ../mldhip.hip, in this order: state, params, dispatch,
-// path_loop, streams, path_vae, path_latent, path_novae, path_clip, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace).
+// path_loop, streams, path_vae, path_latent, path_novae, path_clip, path_eval, path_smpl, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace).
 #pragma once
 #if !defined(MLDHIP_SIM)
 #include <fcntl.h>
@@ -134,6 +134,8 @@ const char* config_error(const mldhip_config* cfg) {
     if (cfg->t2m_max_motions < 1 || cfg->t2m_max_motions > (1 << 20)) return "evaluator towers: t2m_max_motions must be 1 .. 2^20";
     if (cfg->t2m_max_words < 1 || cfg->t2m_max_words > 1024) return "evaluator towers: t2m_max_words must be 1 .. 1024";
   }
+  if (cfg->smpl_verts < 0 || cfg->smpl_verts > 16384) return "smpl_verts must be 0 (no body model) .. 16384";
+  if (cfg->smpl_verts > 0 && cfg->nfeats != 150) return "body model: nfeats must be 150 (25 slots x 6: rot6d of 24 joints + the translation slot)";
   return nullptr;
 }
 
@@ -222,6 +224,14 @@ void carve_eval(E* e, Carver& want) {
   want(&e->vGi, std::max<size_t>(Bc * R2 * 6 * kEvalMotionH, Bc * (size_t)c.t2m_max_words * 6 * kEvalTextH));
   want(&e->vH0, Bc * 2 * kEvalMotionH); want(&e->vH1, Bc * 2 * kEvalMotionH); want(&e->vHead, Bc * kEvalMotionH);
   want(&e->vTab, 3 * Bc);      // ints: rows per motion behind each convolution, GRU steps per motion
+}
+
+// workspace of the SMPL body model (engine/path_smpl.hpp), carved only when smpl_verts > 0: one chunk of frames
+void carve_smpl(E* e, Carver& want) {
+  if (e->cfg.smpl_verts <= 0) return;
+  const size_t F = (size_t)smpl_chunk_frames(e), tiles = F / 16;
+  want(&e->sPf, tiles * kSmplPfTile); want(&e->sA, tiles * kSmplATile); want(&e->sAux, F * 4);
+  want(&e->sTab, (size_t)e->cfg.max_batch);      // ints: the call's lengths
 }
 
 // Kernels launched with more dynamic LDS than the default limit register their size once per process and device (tests/test_cabi.py compares this list
@@ -392,6 +402,7 @@ int create_engine(const mldhip_config& cfg, int device, int num_cus, mldhip_hand
   else carve_latent(e, want);
   carve_clip(e, want);
   carve_eval(e, want);
+  carve_smpl(e, want);
   const size_t Bm = cfg.max_batch;
   e->ws_floats = want.off;
   e->ctxs.resize(cfg.max_in_flight);

@@ -1,6 +1,6 @@
 // Weight contract (SURVEY.md App. B key names), layer binding, scheduler tables, workspace-context plumbing.
 // Part of libmldhip's single translation unit (included by ../mldhip.hip, in this order: state, params, dispatch,
-// path_loop, streams, path_vae, path_latent, path_novae, path_clip, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace) except the handle type itself.
+// path_loop, streams, path_vae, path_latent, path_novae, path_clip, path_eval, path_smpl, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace) except the handle type itself.
 #pragma once
 #include <mutex>
 
@@ -142,7 +142,7 @@ size_t add_param(E* e, const std::string& key, std::vector<int64_t> shape) {
   const bool enc = key.rfind("vae.encoder.", 0) == 0 || key.rfind("vae.skel_embedding.", 0) == 0 ||
                    key.rfind("vae.global_motion_token", 0) == 0 || key.rfind("vae.query_pos_encoder.", 0) == 0;
   const bool ev_text = key.rfind("t2m_textencoder.", 0) == 0, ev_motion = !ev_text && (key.rfind("t2m_", 0) == 0 || key == "mean_eval" || key == "std_eval");
-  p.group = ev_text ? 6 : ev_motion ? 5 : key.rfind("denoiser.", 0) == 0 ? 0 : enc ? 3 : key.rfind("vae.", 0) == 0 ? 1 : key.rfind("text_encoder.", 0) == 0 ? 4 : 2;
+  p.group = key.rfind("smpl.", 0) == 0 ? 7 : ev_text ? 6 : ev_motion ? 5 : key.rfind("denoiser.", 0) == 0 ? 0 : enc ? 3 : key.rfind("vae.", 0) == 0 ? 1 : key.rfind("text_encoder.", 0) == 0 ? 4 : 2;
   e->arena_floats += align_up(p.numel);
   e->index[key] = int(e->params.size());
   e->params.push_back(p);
@@ -207,10 +207,28 @@ void declare_t2m_params(E* e) {
   add_param(e, "std_eval", {NF});
 }
 
+// The SMPL body model's tensors (smpl_verts = V > 0), float32: smplx's buffers (posedirs already [207][3V]); the kinematic tree as floats (parents[0] = -1)
+#if defined(MLDHIP_SIM)
+constexpr int kSmplChunk = 64;       // (the functional simulator's tests reach the chunk loop with 65 frames)
+constexpr int kSmplLaneBudget = 2;   // (... and the multi-block walk of the vertex kernel from V = 129 on)
+#else
+constexpr int kSmplChunk = 4096;     // frames per pass of mldhip_smpl_forward (workspace bound: 8 MB of operands; the numbers do not depend on it)
+constexpr int kSmplLaneBudget = 512; // vertex-kernel workgroups per call: frame groups x vertex-block lanes (two per CU); the numbers do not depend on it
+#endif
+void declare_smpl_params(E* e) {
+  const int64_t V = e->cfg.smpl_verts;
+  add_param(e, "smpl.v_template", {V, 3});
+  add_param(e, "smpl.posedirs", {(int64_t)kSmplK, 3 * V});
+  add_param(e, "smpl.J_regressor", {(int64_t)kSmplJoints, V});
+  add_param(e, "smpl.lbs_weights", {V, (int64_t)kSmplJoints});
+  add_param(e, "smpl.parents", {(int64_t)kSmplJoints});
+}
+
 void declare_params(E* e) {
   declare_model_params(e);
   if (e->cfg.clip_layers > 0) declare_clip_params(e);
   if (e->cfg.t2m_eval) declare_t2m_params(e);
+  if (e->cfg.smpl_verts > 0) declare_smpl_params(e);
 }
 void declare_model_params(E* e) {
   const auto& c = e->cfg;

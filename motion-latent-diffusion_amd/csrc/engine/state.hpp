@@ -13,7 +13,7 @@ struct Param {
   size_t offset = 0;   // floats into the arena
   size_t numel = 0;
   bool loaded = false;
-  int group = 0;       // 0 denoiser, 1 vae decoder, 2 dataset statistics, 3 vae encoder, 4 CLIP text tower, 5 T2M motion evaluators (+ mean_eval / std_eval), 6 T2M text evaluator
+  int group = 0;       // 0 denoiser, 1 vae decoder, 2 dataset statistics, 3 vae encoder, 4 CLIP text tower, 5 T2M motion evaluators (+ mean_eval / std_eval), 6 T2M text evaluator, 7 SMPL body model
 };
 
 struct EncLayerP {   // TransformerEncoderLayer (cross_attention.py:236-272)
@@ -56,6 +56,7 @@ struct WsContext {
   std::vector<StartRow> starts_host;   // stable host copy of what is uploaded to `starts`
   std::vector<int32_t> clip_tab_host;  // text tower: stable host copy of the call's row / prompt tables (engine/path_clip.hpp)
   std::vector<int32_t> eval_tab_host;  // evaluator towers: stable host copy of the call's length tables (engine/path_eval.hpp)
+  std::vector<int32_t> smpl_tab_host;  // body model: stable host copy of the call's lengths (engine/path_smpl.hpp)
   bool used = false;
   unsigned long long seed_host = 0;   // stable host copy of the Philox seed while it is uploaded to seed_slot
 #if !defined(MLDHIP_SIM)
@@ -76,8 +77,8 @@ struct mldhip_engine {
   int device = 0;
   std::string err;
   bool finalized = false;
-  static constexpr int kGroups = 7;
-  bool group_ready[kGroups] = {false, false, false, false, false, false, false};   // denoiser, vae decoder, mean/std, vae encoder, CLIP text tower (clip_layers > 0), T2M motion / text evaluators (t2m_eval = 1)
+  static constexpr int kGroups = 8;
+  bool group_ready[kGroups] = {false, false, false, false, false, false, false, false};   // denoiser, vae decoder, mean/std, vae encoder, CLIP text tower (clip_layers > 0), T2M motion / text evaluators (t2m_eval = 1), SMPL body model (smpl_verts > 0)
 
   // ---- parameters
   std::vector<Param> params;
@@ -109,6 +110,8 @@ struct mldhip_engine {
   int cluster_failed = 0;         // a cluster launch reported a timeout / a placement it cannot use: the handle stays on the other loop families
   float* eval_tabs = nullptr;     // evaluator towers: tables derived from the weights at finalize (tap-major convolution weights, the text tower's input_emb padded to K = 384, the folded GRU input biases)
   float *ev_conv1_w = nullptr, *ev_conv2_w = nullptr, *ev_text_in_w = nullptr, *ev_mbias = nullptr, *ev_tbias = nullptr;   // ... views into it
+  float* smpl_tabs = nullptr;     // body model: tables derived from the smpl.* tensors at finalize (engine/path_smpl.hpp) ...
+  float *sm_P = nullptr, *sm_W = nullptr, *sm_vt = nullptr, *sm_small = nullptr;   // ... views into it: posedirs / lbs_weights / v_template re-laid per 16-vertex block; J [24][3] | J_i - J_parent(i) [24][3] | parents [24] (ints)
   float* arena_x3 = nullptr;  // split-f16 (hi | lo half) image of the arena (precision modes with split-f16 staged GEMMs; built by finalize)
   size_t arena_floats = 0;
   std::vector<EncLayerP> den;      // execution order
@@ -150,6 +153,9 @@ struct mldhip_engine {
   // T2M evaluator towers (t2m_eval = 1; engine/path_eval.hpp), sized for one chunk of kEvalChunk motions: convolution staging G0 / G1, row buffers A / B (512 .. 1024 wide),
   // the input-side gate products Gi [rows][6H], the double-buffered state h0 / h1 [motions][2H], the head's rows, int tables
   float *vG0 = nullptr, *vG1 = nullptr, *vA = nullptr, *vB = nullptr, *vGi = nullptr, *vH0 = nullptr, *vH1 = nullptr, *vHead = nullptr, *vTab = nullptr;
+  // SMPL body model (smpl_verts > 0; engine/path_smpl.hpp), sized for one chunk of frames: pose features [tiles][208][16], skinning matrices [tiles][12][24][16],
+  // per-frame state and translation [frames][4], the call's lengths (ints)
+  float *sPf = nullptr, *sA = nullptr, *sAux = nullptr, *sTab = nullptr;
   float* len_rep = nullptr;   // [max_batch] ints: first sample of each sample's length (length_reps_kernel; decoder layer 0 under "dec_lean")
   float* FS = nullptr;   // sample-major loop: parked skip activations [ceil(max_batch / 8)][nb][48][256]
   float *cl_xbuf = nullptr, *cl_park = nullptr, *cl_flags = nullptr;   // cluster loop: exchange regions [clusters][kClXFloats], parked skip rows [workgroups][nb][16][256], flags [clusters][64] + status [16] (words)
@@ -222,7 +228,7 @@ struct mldhip_engine {
   // every device allocation the handle owns outside its contexts: teardown frees what is listed HERE (a new buffer is added beside its declaration, nowhere else)
   std::vector<void**> device_buffers() {
     return {(void**)&arena, (void**)&arena_x3, (void**)&ffn_streams, (void**)&loop_stream, (void**)&loop_stream_x3, (void**)&cl_stream,
-            (void**)&cl_wave_off_dev, (void**)&loop_small, (void**)&trace_buf, (void**)&nonfinite, (void**)&eval_tabs};
+            (void**)&cl_wave_off_dev, (void**)&loop_small, (void**)&trace_buf, (void**)&nonfinite, (void**)&eval_tabs, (void**)&smpl_tabs};
   }
 
   int fail(int code, const char* fmt, ...) {

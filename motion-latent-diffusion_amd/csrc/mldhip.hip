@@ -12,7 +12,7 @@
 //
 // Source layout: engine/state.hpp (handle, contexts) -> engine/params.hpp (weight contract, schedules) ->
 // engine/dispatch.hpp (kernel selection, the counted launch) -> engine/path_loop.hpp (the latent models' reverse loop) -> engine/streams.hpp (finalize-time weight
-// images) -> engine/path_vae.hpp (VAE decode / encode, feats2joints) -> engine/path_latent.hpp / engine/path_novae.hpp / engine/path_clip.hpp / engine/path_eval.hpp (the sample calls, the text tower, the T2M evaluator towers) ->
+// images) -> engine/path_vae.hpp (VAE decode / encode, feats2joints) -> engine/path_latent.hpp / engine/path_novae.hpp / engine/path_clip.hpp / engine/path_eval.hpp / engine/path_smpl.hpp (the sample calls, the text tower, the T2M evaluator towers, the SMPL body model) ->
 // engine/graphs.hpp (graph capture and caches) -> engine/create.hpp (validation, workspace carve, LDS registration, teardown) ->
 // engine/serve.hpp (the sampling drivers and their shared host sequences) -> engine/probe.hpp (range probe) -> the C ABI below: each
 // entry point is its argument checks and a call into the engine.  kernels/*.hpp hold the device code (no __global__ in this file).
@@ -52,6 +52,7 @@
 #include "kernels/dec_half.hpp"
 #include "kernels/clip_text.hpp"
 #include "kernels/gru.hpp"
+#include "kernels/smpl.hpp"
 
 using namespace mld;
 
@@ -65,6 +66,7 @@ using namespace mld;
 #include "engine/path_novae.hpp"
 #include "engine/path_clip.hpp"
 #include "engine/path_eval.hpp"
+#include "engine/path_smpl.hpp"
 #include "engine/graphs.hpp"
 #include "engine/create.hpp"
 #include "engine/serve.hpp"
@@ -93,6 +95,7 @@ void mldhip_default_config(mldhip_config* c) {
   c->clip_layers = 0; c->clip_heads = 12; c->clip_ff = 3072; c->clip_vocab = 49408; c->clip_ctx = 77; c->clip_max_prompts = 0;
   // no T2M evaluator towers by default (t2m_eval 0); t2m_max_motions 0 = 2 x max_batch, t2m_max_words 0 = 32
   c->t2m_eval = 0; c->t2m_max_motions = 0; c->t2m_max_words = 0;
+  c->smpl_verts = 0;      // no SMPL body model by default
 }
 
 const char* mldhip_last_error(mldhip_handle* h) { return h ? h->err.c_str() : g_last_error.c_str(); }
@@ -104,7 +107,9 @@ int mldhip_create(const mldhip_config* cfg, int device, mldhip_handle** out) {
   // ABI 7 appended the clip_* fields: a caller built against ABI 6 passes the struct that ends behind eta (no text tower then)
   // the t2m_* fields came behind the clip_* fields without a new ABI number: a caller built before them passes the struct that ends behind clip_max_prompts (no evaluators then)
   constexpr int32_t kCfgAbi5 = (int32_t)offsetof(mldhip_config, eta), kCfgAbi6 = (int32_t)offsetof(mldhip_config, clip_layers), kCfgNoEval = (int32_t)offsetof(mldhip_config, t2m_eval);
-  if (cfg->struct_size != (int32_t)sizeof(mldhip_config) && cfg->struct_size != kCfgAbi5 && cfg->struct_size != kCfgAbi6 && cfg->struct_size != kCfgNoEval) return bad("mldhip_config.struct_size mismatch (ABI skew)");
+  // ... and smpl_verts behind the t2m_* fields, the same way: the struct that ends behind t2m_max_words means no body model
+  constexpr int32_t kCfgNoSmpl = (int32_t)offsetof(mldhip_config, smpl_verts);
+  if (cfg->struct_size != (int32_t)sizeof(mldhip_config) && cfg->struct_size != kCfgAbi5 && cfg->struct_size != kCfgAbi6 && cfg->struct_size != kCfgNoEval && cfg->struct_size != kCfgNoSmpl) return bad("mldhip_config.struct_size mismatch (ABI skew)");
   mldhip_config full;
   mldhip_default_config(&full);                       // fields the caller's struct does not cover keep their defaults ...
   if (cfg->struct_size == kCfgAbi5) full.eta = 0.0f;
@@ -131,7 +136,7 @@ int mldhip_load_tensor(mldhip_handle* e, const char* key, const void* data, cons
   auto it = e->index.find(key);
   if (it == e->index.end()) {
     static const char* ignorable[] = {
-                                      "denoiser.mem_pos.", "text_encoder.", "t2m_", "vae.dist_layer."};
+                                      "denoiser.mem_pos.", "text_encoder.", "t2m_", "vae.dist_layer.", "smpl."};
     for (auto p : ignorable)
       if (std::strncmp(key, p, std::strlen(p)) == 0) return 1;
     return e->fail(MLDHIP_EINVAL, "unexpected key %s", key);
@@ -302,6 +307,7 @@ int mldhip_finalize_weights(mldhip_handle* e, void* stream_) {
   if (int rc = build_cluster_stream(c)) return rc;
   if (int rc = build_ffn_streams(c)) return rc;
   if (int rc = build_eval_tables(c)) return rc;
+  if (int rc = build_smpl_tables(c)) return rc;
   for (int k = 0; k < (int)e->ctxs.size(); ++k) {       // the derived tables live in each context's workspace
   bind_context(e, k);
   if (e->group_ready[0]) {
@@ -657,6 +663,13 @@ int mldhip_t2m_text_embed(mldhip_handle* e, const float* word_embs_dev, const fl
   if (!e) return MLDHIP_EINVAL;
   DeviceGuard dg(e->device);
   return t2m_text_embed_impl(e, word_embs_dev, pos_ohot_dev, text_lengths_host, B, L, emb_out_dev, (hipStream_t)stream_);
+}
+
+int mldhip_smpl_forward(mldhip_handle* e, const float* feats_dev, const int32_t* lengths_host, int32_t B, int32_t T, int32_t flags, float* joints_out_dev,
+                        float* verts_out_dev, void* stream_) {
+  if (!e) return MLDHIP_EINVAL;
+  DeviceGuard dg(e->device);
+  return smpl_forward_impl(e, feats_dev, lengths_host, B, T, flags, joints_out_dev, verts_out_dev, (hipStream_t)stream_);
 }
 
 int mldhip_feats2joints(mldhip_handle* e, const float* feats_dev, int32_t B, int32_t T, float* joints_out_dev, void* stream_) {

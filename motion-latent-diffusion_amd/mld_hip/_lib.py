@@ -38,6 +38,7 @@ class Config(C.Structure):
         ("clip_layers", C.c_int32), ("clip_heads", C.c_int32), ("clip_ff", C.c_int32), ("clip_vocab", C.c_int32),
         ("clip_ctx", C.c_int32), ("clip_max_prompts", C.c_int32),
         ("t2m_eval", C.c_int32), ("t2m_max_motions", C.c_int32), ("t2m_max_words", C.c_int32),
+        ("smpl_verts", C.c_int32),
     ]
 
 
@@ -72,6 +73,7 @@ COND_TEXT, COND_ACTION = 0, 1            # MLDHIP_COND_*
 VAE_MLD, VAE_ACTOR, VAE_NONE = 0, 1, 2   # MLDHIP_VAE_*
 ARCH_TRANS_ENC, ARCH_TRANS_DEC = 0, 1    # MLDHIP_ARCH_*
 SCHED_DDIM, SCHED_DDPM = 0, 1            # MLDHIP_SCHED_*
+SMPL_TRANS_JOINTS, SMPL_TRANS_VERTS = 1, 2   # MLDHIP_SMPL_TRANS_*
 
 
 _SYMBOLS = {
@@ -115,6 +117,7 @@ _SYMBOLS = {
     "mldhip_text_encode": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_void_p]),
     "mldhip_t2m_motion_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "mldhip_t2m_text_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mldhip_smpl_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mldhip_feats2joints": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "mldhip_get_timesteps": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]),
     "mldhip_get_alphas_cumprod": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int32]),
@@ -412,6 +415,15 @@ class Engine:
         host (each 1 .. L), ``out`` [B, 512] on the device."""
         lens = (C.c_int32 * len(text_lengths))(*[int(x) for x in text_lengths])
         self._check(self.lib.mldhip_t2m_text_embed(self._h, _ptr(word_embs), _ptr(pos_ohot), lens, len(text_lengths), int(L), _ptr(out), stream))
+
+    def smpl_forward(self, feats, lengths: Sequence[int], T: int, joints_out=None, verts_out=None, flags: int = 0, stream: int = 0):
+        """The SMPL body model (mldhip_smpl_forward; engines created with smpl_verts=V): ``feats`` [B, T, 150] rot6d features on the device, ``lengths`` [B] on
+        the host (each 1 .. T), ``joints_out`` [B, T, 24, 3] and / or ``verts_out`` [B, T, V, 3] on the device (None: not computed), ``flags`` a sum of
+        SMPL_TRANS_JOINTS / SMPL_TRANS_VERTS (add trans[t] - trans[0] to every frame of that output)."""
+        if not hasattr(self.lib, "mldhip_smpl_forward"):
+            raise MldHipError(-2, "this libmldhip has no mldhip_smpl_forward")
+        lens = (C.c_int32 * len(lengths))(*[int(x) for x in lengths])
+        self._check(self.lib.mldhip_smpl_forward(self._h, _ptr(feats), lens, len(lengths), int(T), int(flags), _ptr(joints_out), _ptr(verts_out), stream))
 
     def feats2joints(self, feats, B: int, T: int, joints_out, stream: int = 0):
         self._check(self.lib.mldhip_feats2joints(self._h, _ptr(feats), B, T, _ptr(joints_out), stream))

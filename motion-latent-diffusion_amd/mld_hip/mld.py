@@ -60,14 +60,17 @@ class MLD(nn.Module):
         # the T2M evaluator nets (mld.py:110-140) are opt-in: cfg.model.t2m_evaluator.target = mld_hip.evaluators.HipT2MEvaluator; without it t2m_* keys are dropped
         ev = cfg.model.get("t2m_evaluator") if hasattr(cfg.model, "get") else None
         self.t2m_evaluator = instantiate_from_config(ev) if ev and ev.get("target") else None
-        for m in (self.vae, self.denoiser, self.text_encoder, self.t2m_evaluator):
+        # the SMPL body model (mld.py:118-143: Rotation2xyz) is opt-in too: cfg.model.smpl.target = mld_hip.smpl.HipSmpl, on action models
+        sm = cfg.model.get("smpl") if hasattr(cfg.model, "get") else None
+        self.smpl = instantiate_from_config(sm) if sm and sm.get("target") and self.condition == "action" else None
+        for m in (self.vae, self.denoiser, self.text_encoder, self.t2m_evaluator, self.smpl):
             if engine_key is not None and m is not None and hasattr(m, "use_engine"):
                 m.use_engine(engine_key)
         # ONE engine for all parts of this model: every part asks the registry for the union of the architecture fields
         # (the fused sample() needs every weight group in one handle); another model with other fields gets its own engine
         shared = {}
         # (the datamodule first: its skeleton -- njoints, the feature width -- then the networks'; a HipMldTextEncoder adds the tower's fields: its weights live in the same handle)
-        for m in (datamodule, self.denoiser, self.vae, self.text_encoder, self.t2m_evaluator):
+        for m in (datamodule, self.denoiser, self.vae, self.text_encoder, self.t2m_evaluator, self.smpl):
             shared.update(getattr(m, "_arch", {}) or {})
         if hasattr(self.scheduler, "engine_config"):
             shared.update(self.scheduler.engine_config(cfg.model.scheduler.num_inference_timesteps))
@@ -79,7 +82,7 @@ class MLD(nn.Module):
             self.eta = 0.0
         if self.vae_type != "no":
             shared["eta"] = self.eta
-        for m in (self.denoiser, self.vae, datamodule, self.scheduler, self.text_encoder, self.t2m_evaluator):
+        for m in (self.denoiser, self.vae, datamodule, self.scheduler, self.text_encoder, self.t2m_evaluator, self.smpl):
             if m is not None and hasattr(m, "_shared_arch") and engine_key is None:
                 m._shared_arch = shared
         if hasattr(self.text_encoder, "_shared_arch"):
@@ -94,13 +97,26 @@ class MLD(nn.Module):
         self.fact = None
         self.do_classifier_free_guidance = self.guidance_scale > 1.0
         self.feats2joints = datamodule.feats2joints
+        if self.smpl is not None:                                               # mld.py:118-143
+            self.smpl._variant = self.variant
+            self.rot2xyz = self.smpl.rot2xyz
+            self.feats2joints_eval = lambda sample, mask: self.rot2xyz(
+                sample.view(*sample.shape[:-1], 6, 25).permute(0, 3, 2, 1), mask=mask, pose_rep='rot6d', glob=True, translation=True,
+                jointstype='smpl', vertstrans=True, betas=None, beta=0, glob_rot=None, get_rotations_back=False)
+            self.feats2joints = lambda sample, mask: self.rot2xyz(
+                sample.view(*sample.shape[:-1], 6, 25).permute(0, 3, 2, 1), mask=mask, pose_rep='rot6d', glob=True, translation=True,
+                jointstype='vertices', vertstrans=False, betas=None, beta=0, glob_rot=None, get_rotations_back=False)
         self.times: List[float] = []
 
     # ------------------------------------------------------------------ checkpoint contract (base.py:96-127)
     def load_state_dict(self, state_dict, strict: bool = True):
         te = self.text_encoder.state_dict() if self.text_encoder is not None else {}
         new = OrderedDict(("text_encoder." + k, v) for k, v in te.items())
+        if self.smpl is not None:      # the body model is an asset of its own (SMPL_PATH), never part of a checkpoint: it keeps what it holds
+            new.update(("smpl." + k, v) for k, v in self.smpl.state_dict().items())
         for k, v in state_dict.items():
+            if k.startswith("rot2xyz.") or k.startswith("smpl."):
+                continue
             if k.startswith("t2m_"):      # evaluator nets: loaded (strictly) when the model carries a HipT2MEvaluator, dropped otherwise -- they are not part of sampling
                 if self.t2m_evaluator is not None:
                     new["t2m_evaluator." + k] = v
@@ -123,6 +139,8 @@ class MLD(nn.Module):
             self.vae.sync_weights()
         if self.t2m_evaluator is not None:
             self.t2m_evaluator.sync_weights()
+        if self.smpl is not None:
+            self.smpl.sync_weights()
         want = self.scheduler.engine_config(self.cfg.model.scheduler.num_inference_timesteps)
         for k in ("num_train_timesteps", "num_inference_steps", "steps_offset", "set_alpha_to_one"):
             if getattr(eng.cfg, k) != want[k]:
@@ -378,8 +396,10 @@ class MLD(nn.Module):
     @torch.no_grad()
     def a2m_eval(self, batch, init_latents: Optional[torch.Tensor] = None, seed: Optional[int] = None, first_index: int = 0):
         """Sampling core of MLD.a2m_eval (mld.py:710-735): batch["action"] [B, 1] labels, batch["length"] -> rs_set with
-        ``m_action`` / ``m_rst`` (features [B, T, nfeats]) / ``m_lens``.  The joints entries of the reference's rs_set go
-        through SMPL (mld/transforms/rots2joints/smplh.py) and are not produced here."""
+        ``m_action`` / ``m_rst`` (features [B, T, nfeats]) / ``m_lens``.  The joints entries of the reference's rs_set go through the SMPL body model:
+        with a ``HipSmpl`` on the model (cfg.model.smpl.target, opt-in) the set also holds ``joints_rst`` [B, V, 3, T] (vertices, no translation) and
+        ``joints_eval_rst`` [B, 24, 3, T] (joints, translation), and -- when the batch carries ``"motion"`` -- ``m_ref`` / ``joints_ref`` / ``joints_eval_ref``
+        (mld.py:735-750; the mask is batch["mask"], or the prefix mask of the lengths).  Without it they are not produced."""
         actions, lengths = batch["action"], list(batch["length"])
         if self.fused:
             noise_kw = {} if self.eta == 0.0 else {"seed": seed, "first_index": first_index}
@@ -390,7 +410,18 @@ class MLD(nn.Module):
             cond = torch.cat((torch.zeros_like(a), a)) if self.do_classifier_free_guidance else a      # mld.py:716-717
             z = self._diffusion_reverse(cond.reshape(-1, 1), lengths, init_latents)
             feats = self.vae.decode(z.contiguous(), lengths)
-        return {"m_action": actions, "m_rst": feats, "m_lens": lengths}
+        rs = {"m_action": actions, "m_rst": feats, "m_lens": lengths}
+        if self.smpl is None:
+            return rs
+        mask = batch["mask"] if "mask" in batch else torch.arange(feats.shape[1])[None, :] < torch.tensor([int(n) for n in lengths])[:, None]
+        rs["joints_rst"] = self.feats2joints(feats, mask)                       # mld.py:735-739
+        rs["joints_eval_rst"] = self.feats2joints_eval(feats, mask)
+        if "motion" in batch:
+            motions = batch["motion"].detach().clone().float().to(feats.device)
+            rs["m_ref"] = motions
+            rs["joints_ref"] = self.feats2joints(motions, mask)
+            rs["joints_eval_ref"] = self.feats2joints_eval(motions, mask)
+        return rs
 
     @torch.no_grad()
     def t2m_eval(self, batch, init_latents: Optional[torch.Tensor] = None, seed: Optional[int] = None):

@@ -347,3 +347,47 @@ def make_batch(batch: int, lengths=None, seed: int = 1234, max_len: int = 196,
         lens = [int(x) for x in lengths]
         assert len(lens) == batch
     return SyntheticBatch(text, lat, lens)
+
+
+# ------------------------------------------------------------------------------------------ SMPL body model (mld_hip.smpl.HipSmpl; mldhip_smpl_forward)
+# SMPL's kinematic tree (24 joints: pelvis, hips, spine, knees, ..., wrists, hands) and a rough rest skeleton in metres
+SMPL_PARENTS = (-1, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 9, 12, 13, 14, 16, 17, 18, 19, 20, 21)
+_SMPL_SKELETON = (
+    (0.00, -0.24, 0.03), (0.06, -0.32, 0.02), (-0.06, -0.32, 0.02), (0.00, -0.11, -0.01), (0.10, -0.70, 0.02), (-0.10, -0.70, 0.02),
+    (0.00, 0.02, 0.02), (0.09, -1.10, -0.03), (-0.09, -1.10, -0.03), (0.00, 0.07, 0.04), (0.11, -1.16, 0.09), (-0.11, -1.16, 0.09),
+    (0.00, 0.28, 0.00), (0.08, 0.19, 0.00), (-0.08, 0.19, 0.00), (0.00, 0.36, 0.04), (0.17, 0.22, -0.01), (-0.17, 0.22, -0.01),
+    (0.43, 0.21, -0.03), (-0.43, 0.21, -0.03), (0.68, 0.22, -0.02), (-0.68, 0.22, -0.02), (0.77, 0.21, -0.03), (-0.77, 0.21, -0.03))
+
+
+def make_smpl(V: int = 6890, seed: int = 11, dense: bool = False) -> Dict[str, np.ndarray]:
+    """A seeded stand-in for the SMPL body (no SMPL file is reachable offline), in the engine's tensor contract (include/mldhip.h, keys without the
+    ``smpl.`` prefix): SMPL's 24-joint tree; ``v_template`` [V, 3] scattered around a plausible rest skeleton (vertex v belongs to joint v % 24);
+    ``J_regressor`` [24, V] row-stochastic and sparse; ``lbs_weights`` [V, 24] with rows summing to 1 and at most 4 non-zeros (the vertex's joint, its
+    parent, one child, one more) -- ``dense=True``: all 24 positive; ``posedirs`` [207, 3V] ~ 1e-2 N(0, 1); ``parents`` [24] as float32."""
+    V = int(V)
+    parents = np.asarray(SMPL_PARENTS, np.int64)
+    skel = np.asarray(_SMPL_SKELETON, np.float64)
+    own = np.arange(V) % 24
+    vt = skel[own] + 0.06 * _rng(seed, "smpl.v_template").standard_normal((V, 3))
+    g = _rng(seed, "smpl.J_regressor")
+    jreg = np.zeros((24, V))
+    for j in range(24):
+        idx = g.choice(V, size=min(V, 12), replace=False)
+        w = g.uniform(0.2, 1.0, size=idx.size)
+        jreg[j, idx] = w / w.sum()
+    g = _rng(seed, "smpl.lbs_weights")
+    if dense:
+        lbs = g.uniform(0.05, 1.0, size=(V, 24))
+        lbs[np.arange(V), own] += 4.0
+    else:
+        lbs = np.zeros((V, 24))
+        child = np.asarray([int(np.flatnonzero(parents == j)[0]) if (parents == j).any() else j for j in range(24)])
+        for v in range(V):
+            j = int(own[v])
+            picks = {j, int(max(parents[j], 0)), int(child[j]), int(g.integers(0, 24))}
+            for q in picks:
+                lbs[v, q] = g.uniform(0.1, 1.0) + (2.0 if q == j else 0.0)
+    lbs /= lbs.sum(axis=1, keepdims=True)
+    posedirs = 1e-2 * _rng(seed, "smpl.posedirs").standard_normal((207, 3 * V))
+    return {"v_template": vt.astype(np.float32), "posedirs": posedirs.astype(np.float32), "J_regressor": jreg.astype(np.float32),
+            "lbs_weights": lbs.astype(np.float32), "parents": parents.astype(np.float32)}
