@@ -158,6 +158,12 @@ typedef struct mldhip_config {
    * the field is otherwise independent of vae_arch / condition. */
   int32_t smpl_verts;           /* 0 (default) = no body model: no weights, no workspace, every smpl.* key accepted and ignored, mis-shaped ones included;
                                  * 1 .. 16384 = V, the vertex count of the body (SMPL: 6890) */
+  /* ---- the optional HumanAct12 action-recognition GRU (mldhip_a2m_recognize below; MLDHIP_ABI_VERSION stays 8: callers detect the feature by the presence of
+   * the symbol).  Read only when struct_size covers them (a caller's struct that ends behind smpl_verts means no recognizer).  Independent of condition / vae_arch. */
+  int32_t a2m_rec;              /* 0 (default) = no recognizer: no weights, no workspace, every a2m_rec.* key accepted and ignored, mis-shaped ones included;
+                                 * 1 = the recognition GRU */
+  int32_t a2m_max_motions;      /* capacity: motions per mldhip_a2m_recognize call; 0 (default) = 4 x max_batch (one metric update's four passes -- the classifier
+                                 * and the FID net on the generated and the ground-truth motions -- in one call) */
 } mldhip_config;
 
 enum { MLDHIP_COND_TEXT = 0, MLDHIP_COND_ACTION = 1 };
@@ -712,6 +718,38 @@ int mldhip_t2m_text_embed(mldhip_handle* h, const float* word_embs_dev /*[B,L,30
 enum { MLDHIP_SMPL_TRANS_JOINTS = 1, MLDHIP_SMPL_TRANS_VERTS = 2 };
 int mldhip_smpl_forward(mldhip_handle* h, const float* feats_dev /*[B,T,150]*/, const int32_t* lengths_host, int32_t B, int32_t T,
                         int32_t flags, float* joints_out_dev /*[B,T,24,3] or NULL*/, float* verts_out_dev /*[B,T,V,3] or NULL*/, void* stream);
+
+/* The HumanAct12 action-recognition GRU (handles created with a2m_rec = 1).  Replaces: MotionDiscriminator / MotionDiscriminatorForFID
+ * (mld/models/architectures/humanact12_gru.py) with input_size 72, hidden_size 128, hidden_layer 2, output_size 12, as HUMANACTMetrics (mld/models/metrics/gru.py)
+ * runs them on the joints of mldhip_smpl_forward.
+ *
+ * WEIGHTS.  One more optional all-or-nothing group, float32, under the names of humanact12_gru.tar's "model" prefixed a2m_rec. (a wrong shape is
+ * MLDHIP_EINVAL, mldhip_missing_keys reports a half-loaded group; with a2m_rec = 0 every a2m_rec.* key is accepted and ignored):
+ *   a2m_rec.recurrent.weight_ih_l0 [384][72];  a2m_rec.recurrent.weight_hh_l0, weight_ih_l1, weight_hh_l1 [384][128];
+ *   a2m_rec.recurrent.bias_ih_l0, bias_hh_l0, bias_ih_l1, bias_hh_l1 [384];  a2m_rec.linear1.weight [30][128], .bias [30];  a2m_rec.linear2.weight [12][30], .bias [12].
+ *
+ * INPUT.  joints [B][T][72]: mldhip_smpl_forward's joints [B][T][24][3] as they are; feature 3 joint + coord (the reference's [B, 24, 3, T] reshaped to
+ * [B, 72, T] and permuted to [T, B, 72]).
+ * MATH.  A 2-layer unidirectional GRU over steps t = 0 .. len - 1 of each motion, PyTorch's cell, gate rows r | z | n of each [384] weight:
+ *   r = sigmoid(W_ir x + b_ir + W_hr h + b_hr);  z = sigmoid(W_iz x + b_iz + W_hz h + b_hz);  n = tanh(W_in x + b_in + r (W_hn h + b_hn));  h' = (1 - z) n + z h;
+ *   layer 1's x is layer 0's h' of the same step.  out = layer 1's state after step len - 1;  act = tanh(linear1(out)) [30];  logits = linear2(act) [12].
+ * THE PADDED-FRAME RULE.  The GRU is causal and the reference reads its output at step len - 1, so frames t >= len never affect the outputs: they are never
+ *   read (NaN there gives the same bits), and a motion's outputs are bit-identical alone, inside any batch and for any T >= len.
+ * THE h0 CONTRACT.  h0_dev [2][B][128] is the initial state of layer 0 ([0][b]) and layer 1 ([1][b]); NULL means zeros.  The reference draws
+ *   h0 = torch.randn(2, B, 128) on the CPU default generator at EVERY forward call (initHidden); the caller draws it the same way and passes it (HUMANACTMetrics
+ *   .update makes four draws -- classifier on the generated motions, on the ground truth, then the FID net on each -- mld_hip.metrics.HipHUMANACTMetrics stacks
+ *   them along B and makes one call of 4B motions).  Logits and activations of a call row come from the same h0 row.
+ *
+ * KERNEL (kernels/a2m_gru.hpp): ONE launch; a workgroup per tile of 16 motions runs both layers over the tile's steps (layer 1 one step behind layer 0, one
+ * barrier per step, both states in LDS), each motion stopping at its own length, then the head on the tile's final states.  ARITHMETIC: exact-fp32 MFMAs
+ * (v_mfma_f32_16x16x4_f32) for the recurrence and fp32 VALU for the head in EVERY precision mode -- no stage of the range contract; an MLDHIP_PREC_F16X3
+ * handle gives the same bits as an MLDHIP_PREC_F32 one.  Reasoning: the work is tiny and latency-bound, and the predicted classes are argmaxes.
+ * The call is stream-ordered and issued eagerly (no hipGraph); lengths reach the kernel through an engine-owned table uploaded with the call; non-finite
+ * output values are counted into the sticky counter of mldhip_numeric_status.
+ * MLDHIP_EINVAL: B outside 1 .. a2m_max_motions, T outside 1 .. max_frames, a length outside 1 .. T, both outputs NULL, a null input.
+ * MLDHIP_ESTATE: no recognizer on the handle, the group not loaded, the handle not finalized. */
+int mldhip_a2m_recognize(mldhip_handle* h, const float* joints_dev /*[B,T,72]*/, const int32_t* lengths_host, const float* h0_dev /*[2,B,128] or NULL = zeros*/,
+                         int32_t B, int32_t T, float* logits_out_dev /*[B,12] or NULL*/, float* act_out_dev /*[B,30] or NULL*/, void* stream);
 
 /* Replaces: HumanML3DDataModule.feats2joints (mld/data/HumanML3D.py:41-45 -> recover_from_ric,
  * mld/data/humanml/scripts/motion_process.py:415-432).  feats [B,T,nfeats] -> joints [B,T,njoints,3]. */

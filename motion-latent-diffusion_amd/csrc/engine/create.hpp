@@ -1,7 +1,7 @@
 // Handle construction and teardown: the cluster-lane lock of a device, config validation, the workspace carve of the two variants,
 // the dynamic-LDS registration list, create_engine / destroy_engine.
 // Part of libmldhip's single translation unit (included by ../mldhip.hip, in this order: state, params, dispatch,
-// path_loop, streams, path_vae, path_latent, path_novae, path_clip, path_eval, path_smpl, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace).
+// path_loop, streams, path_vae, path_latent, path_novae, path_clip, path_eval, path_smpl, path_a2m, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace).
 #pragma once
 #if !defined(MLDHIP_SIM)
 #include <fcntl.h>
@@ -136,6 +136,8 @@ const char* config_error(const mldhip_config* cfg) {
   }
   if (cfg->smpl_verts < 0 || cfg->smpl_verts > 16384) return "smpl_verts must be 0 (no body model) .. 16384";
   if (cfg->smpl_verts > 0 && cfg->nfeats != 150) return "body model: nfeats must be 150 (25 slots x 6: rot6d of 24 joints + the translation slot)";
+  if (cfg->a2m_rec != 0 && cfg->a2m_rec != 1) return "a2m_rec must be 0 (no recognizer) or 1 (the HumanAct12 recognition GRU)";
+  if (cfg->a2m_rec && (cfg->a2m_max_motions < 1 || cfg->a2m_max_motions > (1 << 20))) return "recognition GRU: a2m_max_motions must be 1 .. 2^20";
   return nullptr;
 }
 
@@ -232,6 +234,12 @@ void carve_smpl(E* e, Carver& want) {
   const size_t F = (size_t)smpl_chunk_frames(e), tiles = F / 16;
   want(&e->sPf, tiles * kSmplPfTile); want(&e->sA, tiles * kSmplATile); want(&e->sAux, F * 4);
   want(&e->sTab, (size_t)e->cfg.max_batch);      // ints: the call's lengths
+}
+
+// workspace of the HumanAct12 recognition GRU (engine/path_a2m.hpp), carved only when a2m_rec = 1: the call's lengths
+void carve_a2m(E* e, Carver& want) {
+  if (!e->cfg.a2m_rec) return;
+  want(&e->rTab, (size_t)e->cfg.a2m_max_motions);      // ints
 }
 
 // Kernels launched with more dynamic LDS than the default limit register their size once per process and device (tests/test_cabi.py compares this list
@@ -403,6 +411,7 @@ int create_engine(const mldhip_config& cfg, int device, int num_cus, mldhip_hand
   carve_clip(e, want);
   carve_eval(e, want);
   carve_smpl(e, want);
+  carve_a2m(e, want);
   const size_t Bm = cfg.max_batch;
   e->ws_floats = want.off;
   e->ctxs.resize(cfg.max_in_flight);

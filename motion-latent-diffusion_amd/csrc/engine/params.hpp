@@ -1,6 +1,6 @@
 // Weight contract (SURVEY.md App. B key names), layer binding, scheduler tables, workspace-context plumbing.
 // Part of libmldhip's single translation unit (included by ../mldhip.hip, in this order: state, params, dispatch,
-// path_loop, streams, path_vae, path_latent, path_novae, path_clip, path_eval, path_smpl, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace) except the handle type itself.
+// path_loop, streams, path_vae, path_latent, path_novae, path_clip, path_eval, path_smpl, path_a2m, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace) except the handle type itself.
 #pragma once
 #include <mutex>
 
@@ -142,7 +142,7 @@ size_t add_param(E* e, const std::string& key, std::vector<int64_t> shape) {
   const bool enc = key.rfind("vae.encoder.", 0) == 0 || key.rfind("vae.skel_embedding.", 0) == 0 ||
                    key.rfind("vae.global_motion_token", 0) == 0 || key.rfind("vae.query_pos_encoder.", 0) == 0;
   const bool ev_text = key.rfind("t2m_textencoder.", 0) == 0, ev_motion = !ev_text && (key.rfind("t2m_", 0) == 0 || key == "mean_eval" || key == "std_eval");
-  p.group = key.rfind("smpl.", 0) == 0 ? 7 : ev_text ? 6 : ev_motion ? 5 : key.rfind("denoiser.", 0) == 0 ? 0 : enc ? 3 : key.rfind("vae.", 0) == 0 ? 1 : key.rfind("text_encoder.", 0) == 0 ? 4 : 2;
+  p.group = key.rfind("a2m_rec.", 0) == 0 ? 8 : key.rfind("smpl.", 0) == 0 ? 7 : ev_text ? 6 : ev_motion ? 5 : key.rfind("denoiser.", 0) == 0 ? 0 : enc ? 3 : key.rfind("vae.", 0) == 0 ? 1 : key.rfind("text_encoder.", 0) == 0 ? 4 : 2;
   e->arena_floats += align_up(p.numel);
   e->index[key] = int(e->params.size());
   e->params.push_back(p);
@@ -224,11 +224,24 @@ void declare_smpl_params(E* e) {
   add_param(e, "smpl.parents", {(int64_t)kSmplJoints});
 }
 
+// The HumanAct12 recognition GRU's tensors (a2m_rec = 1) under the names of humanact12_gru.tar's "model", prefixed a2m_rec.
+void declare_a2m_params(E* e) {
+  const std::string p = "a2m_rec.recurrent.";
+  add_param(e, p + "weight_ih_l0", {(int64_t)kA2mG, (int64_t)kA2mIn});
+  add_param(e, p + "weight_hh_l0", {(int64_t)kA2mG, (int64_t)kA2mH});
+  add_param(e, p + "weight_ih_l1", {(int64_t)kA2mG, (int64_t)kA2mH});
+  add_param(e, p + "weight_hh_l1", {(int64_t)kA2mG, (int64_t)kA2mH});
+  for (const char* n : {"bias_ih_l0", "bias_hh_l0", "bias_ih_l1", "bias_hh_l1"}) add_param(e, p + n, {(int64_t)kA2mG});
+  add_param(e, "a2m_rec.linear1.weight", {(int64_t)kA2mL1, (int64_t)kA2mH}); add_param(e, "a2m_rec.linear1.bias", {(int64_t)kA2mL1});
+  add_param(e, "a2m_rec.linear2.weight", {(int64_t)kA2mCls, (int64_t)kA2mL1}); add_param(e, "a2m_rec.linear2.bias", {(int64_t)kA2mCls});
+}
+
 void declare_params(E* e) {
   declare_model_params(e);
   if (e->cfg.clip_layers > 0) declare_clip_params(e);
   if (e->cfg.t2m_eval) declare_t2m_params(e);
   if (e->cfg.smpl_verts > 0) declare_smpl_params(e);
+  if (e->cfg.a2m_rec) declare_a2m_params(e);
 }
 void declare_model_params(E* e) {
   const auto& c = e->cfg;

@@ -13,7 +13,8 @@ struct Param {
   size_t offset = 0;   // floats into the arena
   size_t numel = 0;
   bool loaded = false;
-  int group = 0;       // 0 denoiser, 1 vae decoder, 2 dataset statistics, 3 vae encoder, 4 CLIP text tower, 5 T2M motion evaluators (+ mean_eval / std_eval), 6 T2M text evaluator, 7 SMPL body model
+  int group = 0;       // 0 denoiser, 1 vae decoder, 2 dataset statistics, 3 vae encoder, 4 CLIP text tower, 5 T2M motion evaluators (+ mean_eval / std_eval), 6 T2M text evaluator, 7 SMPL body model,
+                       // 8 HumanAct12 recognition GRU
 };
 
 struct EncLayerP {   // TransformerEncoderLayer (cross_attention.py:236-272)
@@ -57,6 +58,7 @@ struct WsContext {
   std::vector<int32_t> clip_tab_host;  // text tower: stable host copy of the call's row / prompt tables (engine/path_clip.hpp)
   std::vector<int32_t> eval_tab_host;  // evaluator towers: stable host copy of the call's length tables (engine/path_eval.hpp)
   std::vector<int32_t> smpl_tab_host;  // body model: stable host copy of the call's lengths (engine/path_smpl.hpp)
+  std::vector<int32_t> a2m_tab_host;   // recognition GRU: stable host copy of the call's lengths (engine/path_a2m.hpp)
   bool used = false;
   unsigned long long seed_host = 0;   // stable host copy of the Philox seed while it is uploaded to seed_slot
 #if !defined(MLDHIP_SIM)
@@ -77,8 +79,9 @@ struct mldhip_engine {
   int device = 0;
   std::string err;
   bool finalized = false;
-  static constexpr int kGroups = 8;
-  bool group_ready[kGroups] = {false, false, false, false, false, false, false, false};   // denoiser, vae decoder, mean/std, vae encoder, CLIP text tower (clip_layers > 0), T2M motion / text evaluators (t2m_eval = 1), SMPL body model (smpl_verts > 0)
+  static constexpr int kGroups = 9;
+  bool group_ready[kGroups] = {false, false, false, false, false, false, false, false, false};   // denoiser, vae decoder, mean/std, vae encoder, CLIP text tower (clip_layers > 0), T2M motion / text evaluators (t2m_eval = 1), SMPL body model (smpl_verts > 0),
+                                                                                                 // HumanAct12 recognition GRU (a2m_rec = 1)
 
   // ---- parameters
   std::vector<Param> params;
@@ -156,6 +159,7 @@ struct mldhip_engine {
   // SMPL body model (smpl_verts > 0; engine/path_smpl.hpp), sized for one chunk of frames: pose features [tiles][208][16], skinning matrices [tiles][12][24][16],
   // per-frame state and translation [frames][4], the call's lengths (ints)
   float *sPf = nullptr, *sA = nullptr, *sAux = nullptr, *sTab = nullptr;
+  float* rTab = nullptr;      // HumanAct12 recognition GRU (a2m_rec = 1; engine/path_a2m.hpp): the call's lengths (ints, a2m_max_motions of them)
   float* len_rep = nullptr;   // [max_batch] ints: first sample of each sample's length (length_reps_kernel; decoder layer 0 under "dec_lean")
   float* FS = nullptr;   // sample-major loop: parked skip activations [ceil(max_batch / 8)][nb][48][256]
   float *cl_xbuf = nullptr, *cl_park = nullptr, *cl_flags = nullptr;   // cluster loop: exchange regions [clusters][kClXFloats], parked skip rows [workgroups][nb][16][256], flags [clusters][64] + status [16] (words)

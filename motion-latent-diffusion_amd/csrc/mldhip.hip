@@ -12,7 +12,7 @@
 //
 // Source layout: engine/state.hpp (handle, contexts) -> engine/params.hpp (weight contract, schedules) ->
 // engine/dispatch.hpp (kernel selection, the counted launch) -> engine/path_loop.hpp (the latent models' reverse loop) -> engine/streams.hpp (finalize-time weight
-// images) -> engine/path_vae.hpp (VAE decode / encode, feats2joints) -> engine/path_latent.hpp / engine/path_novae.hpp / engine/path_clip.hpp / engine/path_eval.hpp / engine/path_smpl.hpp (the sample calls, the text tower, the T2M evaluator towers, the SMPL body model) ->
+// images) -> engine/path_vae.hpp (VAE decode / encode, feats2joints) -> engine/path_latent.hpp / engine/path_novae.hpp / engine/path_clip.hpp / engine/path_eval.hpp / engine/path_smpl.hpp / engine/path_a2m.hpp (the sample calls, the text tower, the T2M evaluator towers, the SMPL body model, the HumanAct12 recognition GRU) ->
 // engine/graphs.hpp (graph capture and caches) -> engine/create.hpp (validation, workspace carve, LDS registration, teardown) ->
 // engine/serve.hpp (the sampling drivers and their shared host sequences) -> engine/probe.hpp (range probe) -> the C ABI below: each
 // entry point is its argument checks and a call into the engine.  kernels/*.hpp hold the device code (no __global__ in this file).
@@ -53,6 +53,7 @@
 #include "kernels/clip_text.hpp"
 #include "kernels/gru.hpp"
 #include "kernels/smpl.hpp"
+#include "kernels/a2m_gru.hpp"
 
 using namespace mld;
 
@@ -67,6 +68,7 @@ using namespace mld;
 #include "engine/path_clip.hpp"
 #include "engine/path_eval.hpp"
 #include "engine/path_smpl.hpp"
+#include "engine/path_a2m.hpp"
 #include "engine/graphs.hpp"
 #include "engine/create.hpp"
 #include "engine/serve.hpp"
@@ -96,6 +98,7 @@ void mldhip_default_config(mldhip_config* c) {
   // no T2M evaluator towers by default (t2m_eval 0); t2m_max_motions 0 = 2 x max_batch, t2m_max_words 0 = 32
   c->t2m_eval = 0; c->t2m_max_motions = 0; c->t2m_max_words = 0;
   c->smpl_verts = 0;      // no SMPL body model by default
+  c->a2m_rec = 0; c->a2m_max_motions = 0;      // no recognition GRU by default; a2m_max_motions 0 = 4 x max_batch
 }
 
 const char* mldhip_last_error(mldhip_handle* h) { return h ? h->err.c_str() : g_last_error.c_str(); }
@@ -109,7 +112,10 @@ int mldhip_create(const mldhip_config* cfg, int device, mldhip_handle** out) {
   constexpr int32_t kCfgAbi5 = (int32_t)offsetof(mldhip_config, eta), kCfgAbi6 = (int32_t)offsetof(mldhip_config, clip_layers), kCfgNoEval = (int32_t)offsetof(mldhip_config, t2m_eval);
   // ... and smpl_verts behind the t2m_* fields, the same way: the struct that ends behind t2m_max_words means no body model
   constexpr int32_t kCfgNoSmpl = (int32_t)offsetof(mldhip_config, smpl_verts);
-  if (cfg->struct_size != (int32_t)sizeof(mldhip_config) && cfg->struct_size != kCfgAbi5 && cfg->struct_size != kCfgAbi6 && cfg->struct_size != kCfgNoEval && cfg->struct_size != kCfgNoSmpl) return bad("mldhip_config.struct_size mismatch (ABI skew)");
+  // ... and the a2m_* fields behind smpl_verts: the struct that ends behind smpl_verts means no recognizer
+  constexpr int32_t kCfgNoA2m = (int32_t)offsetof(mldhip_config, a2m_rec);
+  if (cfg->struct_size != (int32_t)sizeof(mldhip_config) && cfg->struct_size != kCfgAbi5 && cfg->struct_size != kCfgAbi6 && cfg->struct_size != kCfgNoEval && cfg->struct_size != kCfgNoSmpl &&
+      cfg->struct_size != kCfgNoA2m) return bad("mldhip_config.struct_size mismatch (ABI skew)");
   mldhip_config full;
   mldhip_default_config(&full);                       // fields the caller's struct does not cover keep their defaults ...
   if (cfg->struct_size == kCfgAbi5) full.eta = 0.0f;
@@ -118,6 +124,7 @@ int mldhip_create(const mldhip_config* cfg, int device, mldhip_handle** out) {
   if (full.clip_layers > 0 && full.clip_max_prompts == 0) full.clip_max_prompts = 2 * full.max_batch;
   if (full.t2m_eval && full.t2m_max_motions == 0) full.t2m_max_motions = 2 * full.max_batch;
   if (full.t2m_eval && full.t2m_max_words == 0) full.t2m_max_words = 32;
+  if (full.a2m_rec && full.a2m_max_motions == 0) full.a2m_max_motions = 4 * full.max_batch;
   if (const char* what = config_error(&full)) return bad(what);
   int num_cus = 0;
   if (int rc = check_device(device, &num_cus)) return rc;
@@ -136,7 +143,7 @@ int mldhip_load_tensor(mldhip_handle* e, const char* key, const void* data, cons
   auto it = e->index.find(key);
   if (it == e->index.end()) {
     static const char* ignorable[] = {
-                                      "denoiser.mem_pos.", "text_encoder.", "t2m_", "vae.dist_layer.", "smpl."};
+                                      "denoiser.mem_pos.", "text_encoder.", "t2m_", "vae.dist_layer.", "smpl.", "a2m_rec."};
     for (auto p : ignorable)
       if (std::strncmp(key, p, std::strlen(p)) == 0) return 1;
     return e->fail(MLDHIP_EINVAL, "unexpected key %s", key);
@@ -670,6 +677,13 @@ int mldhip_smpl_forward(mldhip_handle* e, const float* feats_dev, const int32_t*
   if (!e) return MLDHIP_EINVAL;
   DeviceGuard dg(e->device);
   return smpl_forward_impl(e, feats_dev, lengths_host, B, T, flags, joints_out_dev, verts_out_dev, (hipStream_t)stream_);
+}
+
+int mldhip_a2m_recognize(mldhip_handle* e, const float* joints_dev, const int32_t* lengths_host, const float* h0_dev, int32_t B, int32_t T, float* logits_out_dev,
+                         float* act_out_dev, void* stream_) {
+  if (!e) return MLDHIP_EINVAL;
+  DeviceGuard dg(e->device);
+  return a2m_recognize_impl(e, joints_dev, lengths_host, h0_dev, B, T, logits_out_dev, act_out_dev, (hipStream_t)stream_);
 }
 
 int mldhip_feats2joints(mldhip_handle* e, const float* feats_dev, int32_t B, int32_t T, float* joints_out_dev, void* stream_) {

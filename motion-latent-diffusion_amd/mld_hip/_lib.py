@@ -39,6 +39,7 @@ class Config(C.Structure):
         ("clip_ctx", C.c_int32), ("clip_max_prompts", C.c_int32),
         ("t2m_eval", C.c_int32), ("t2m_max_motions", C.c_int32), ("t2m_max_words", C.c_int32),
         ("smpl_verts", C.c_int32),
+        ("a2m_rec", C.c_int32), ("a2m_max_motions", C.c_int32),
     ]
 
 
@@ -118,6 +119,7 @@ _SYMBOLS = {
     "mldhip_t2m_motion_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "mldhip_t2m_text_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "mldhip_smpl_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mldhip_a2m_recognize": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mldhip_feats2joints": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "mldhip_get_timesteps": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]),
     "mldhip_get_alphas_cumprod": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int32]),
@@ -424,6 +426,15 @@ class Engine:
             raise MldHipError(-2, "this libmldhip has no mldhip_smpl_forward")
         lens = (C.c_int32 * len(lengths))(*[int(x) for x in lengths])
         self._check(self.lib.mldhip_smpl_forward(self._h, _ptr(feats), lens, len(lengths), int(T), int(flags), _ptr(joints_out), _ptr(verts_out), stream))
+
+    def a2m_recognize(self, joints, lengths: Sequence[int], T: int, h0=None, logits_out=None, act_out=None, stream: int = 0):
+        """The HumanAct12 recognition GRU (mldhip_a2m_recognize; engines created with a2m_rec=1): ``joints`` [B, T, 72] on the device, ``lengths`` [B] on the
+        host (each 1 .. T), ``h0`` [2, B, 128] on the device (None: zeros), ``logits_out`` [B, 12] and / or ``act_out`` [B, 30] on the device (None: not
+        stored)."""
+        if not hasattr(self.lib, "mldhip_a2m_recognize"):
+            raise MldHipError(-2, "this libmldhip has no mldhip_a2m_recognize")
+        lens = (C.c_int32 * len(lengths))(*[int(x) for x in lengths])
+        self._check(self.lib.mldhip_a2m_recognize(self._h, _ptr(joints), lens, _ptr(h0), len(lengths), int(T), _ptr(logits_out), _ptr(act_out), stream))
 
     def feats2joints(self, feats, B: int, T: int, joints_out, stream: int = 0):
         self._check(self.lib.mldhip_feats2joints(self._h, _ptr(feats), B, T, _ptr(joints_out), stream))

@@ -1,4 +1,6 @@
-"""``HipT2MEvaluator`` -- the pretrained T2M evaluator nets of a checkpoint (``t2m_moveencoder`` / ``t2m_motionencoder`` / ``t2m_textencoder``:
+"""``HipT2MEvaluator`` (below) and ``HipActionRecognizer`` (the HumanAct12 recognition GRU behind mld_hip.metrics.HipHUMANACTMetrics; at the end of this file).
+
+``HipT2MEvaluator`` -- the pretrained T2M evaluator nets of a checkpoint (``t2m_moveencoder`` / ``t2m_motionencoder`` / ``t2m_textencoder``:
 mld/models/architectures/t2m_motionenc.py, t2m_textenc.py; instantiated at mld/models/modeltype/mld.py:110-140) as one drop-in module whose arithmetic
 runs in libmldhip (``mldhip_t2m_motion_embed`` / ``mldhip_t2m_text_embed``; include/mldhip.h has the math).
 
@@ -6,8 +8,11 @@ Opt-in: ``load_config(overrides={"model.t2m_evaluator.target": "mld_hip.evaluato
 checkpoint; with it ``MLD.load_state_dict`` loads them strictly and ``MLD.t2m_eval`` returns the embeddings the T2M metrics are computed from."""
 from __future__ import annotations
 
-from typing import Sequence
+import os
+import warnings
+from typing import Dict, Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import engine as _engine
@@ -58,3 +63,88 @@ class HipT2MEvaluator(HipModule):
         out = torch.empty(w.shape[0], 512, dtype=torch.float32, device=w.device)
         eng.t2m_text_embed(w, p, [int(n) for n in text_lengths], w.shape[1], out, stream=_engine.current_stream_handle(w))
         return out
+
+
+def _find_rec_file(path):
+    if not path:
+        return None
+    if os.path.isfile(path):
+        return path
+    f = os.path.join(path, "humanact12_gru.tar")
+    return f if os.path.isfile(f) else None
+
+
+class HipActionRecognizer(HipModule):
+    """The pretrained HumanAct12 recognition GRU (``humanact12_gru.tar``: MotionDiscriminator(72, 128, 2, 12) / MotionDiscriminatorForFID,
+    mld/models/architectures/humanact12_gru.py) as one module whose arithmetic runs in libmldhip (``mldhip_a2m_recognize``; include/mldhip.h has the math,
+    the padded-frame rule and the h0 contract).  Parameters carry the file's own names (``recurrent.weight_ih_l0``, ..., ``linear2.bias``).
+
+    ``humanact12_rec_path`` (cfg.model.humanact12_rec_path, or the file itself) with a ``humanact12_gru.tar`` in it fills them from the file's ``model``;
+    otherwise they hold ``mld_hip.synthetic.make_a2m_rec_state_dict`` -- a seeded stand-in at PyTorch's default init ranges, since no such file ships with
+    this repository -- and ``source`` says which; a path that holds no such file gets a ``RuntimeWarning`` saying so."""
+    _prefix = "a2m_rec."
+
+    def __init__(self, humanact12_rec_path: Optional[str] = None, seed: int = 12, tensors: Optional[Dict[str, object]] = None, **_):
+        super().__init__()
+        path = _find_rec_file(humanact12_rec_path) if tensors is None else None
+        if tensors is not None:
+            self.source = "tensors"
+        elif path is not None:
+            tensors, self.source = torch.load(path, map_location="cpu")["model"], path
+        else:
+            if humanact12_rec_path:
+                warnings.warn(f"HipActionRecognizer: no humanact12_gru.tar under humanact12_rec_path={humanact12_rec_path!r}; the weights are the seeded "
+                              "synthetic stand-in (source == 'synthetic'), so its classes and activations are not the pretrained net's", RuntimeWarning, stacklevel=2)
+            tensors, self.source = syn.make_a2m_rec_state_dict(seed), "synthetic"
+        want = syn.make_a2m_rec_state_dict(seed)
+        for k, v in want.items():
+            if k not in tensors or tuple(np.shape(tensors[k])) != v.shape:
+                raise ValueError(f"HipActionRecognizer: {k} {tuple(v.shape)} expected (include/mldhip.h)")
+        self._register_tree({k: np.asarray(torch.as_tensor(tensors[k]).float().cpu().numpy(), np.float32) for k in want})
+        self._set_arch("action", a2m_rec=1)
+
+    @staticmethod
+    def capacity(eng) -> int:
+        return int(eng.cfg.a2m_max_motions) or 4 * int(eng.cfg.max_batch)
+
+    @torch.no_grad()
+    def recognize(self, joints: torch.Tensor, lengths: Sequence[int], h0: Optional[torch.Tensor] = None):
+        """joints [B, T, 72] (mldhip_smpl_forward's joints, feature 3 joint + coord), lengths [B], h0 [2, B, 128] (None: zeros) -> (logits [B, 12],
+        activations [B, 30]); a batch beyond the engine's capacity goes through in slices (a motion's rows do not depend on its neighbours)"""
+        j = self._check(joints, "joints")
+        if j.dim() != 3 or j.shape[2] != 72:
+            raise ValueError(f"joints must be [B, T, 72], got {tuple(j.shape)}")
+        lengths = [int(n) for n in lengths]
+        B, T = j.shape[:2]
+        if len(lengths) != B:
+            raise ValueError("one length per motion")
+        if h0 is not None:
+            h0 = self._check(h0.to(j.device), "h0")
+            if tuple(h0.shape) != (2, B, 128):
+                raise ValueError(f"h0 must be [2, B, 128], got {tuple(h0.shape)}")
+        eng = self.sync_weights()
+        logits = torch.empty(B, 12, dtype=torch.float32, device=j.device)
+        act = torch.empty(B, 30, dtype=torch.float32, device=j.device)
+        stream = _engine.current_stream_handle(j)
+        step = self.capacity(eng)
+        for b0 in range(0, B, step):
+            sl = slice(b0, min(B, b0 + step))
+            h = None if h0 is None else (h0 if step >= B else h0[:, sl].contiguous())
+            eng.a2m_recognize(j[sl], lengths[sl], T, h, logits[sl], act[sl], stream)
+        return logits, act
+
+    @staticmethod
+    def to_joints(motion: torch.Tensor) -> torch.Tensor:
+        """the reference's [B, 24, 3, T] -> [B, T, 72]"""
+        B, J, C, T = motion.shape
+        return motion.reshape(B, J * C, T).permute(0, 2, 1).float().contiguous()
+
+    def forward(self, motion_sequence: torch.Tensor, lengths=None, hidden_unit: Optional[torch.Tensor] = None, fid: bool = False):
+        """MotionDiscriminator.forward (``fid``: MotionDiscriminatorForFID.forward): motion [B, 24, 3, T], lengths [B]; without ``hidden_unit`` the initial
+        state is drawn as the reference draws it, torch.randn(2, B, 128) on the CPU default generator"""
+        B, T = motion_sequence.shape[0], motion_sequence.shape[3]
+        if hidden_unit is None:
+            hidden_unit = torch.randn(2, B, 128, requires_grad=False)
+        lengths = [T] * B if lengths is None else [int(n) for n in lengths]
+        logits, act = self.recognize(self.to_joints(motion_sequence), lengths, hidden_unit.float())
+        return act if fid else logits

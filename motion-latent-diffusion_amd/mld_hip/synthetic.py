@@ -391,3 +391,25 @@ def make_smpl(V: int = 6890, seed: int = 11, dense: bool = False) -> Dict[str, n
     posedirs = 1e-2 * _rng(seed, "smpl.posedirs").standard_normal((207, 3 * V))
     return {"v_template": vt.astype(np.float32), "posedirs": posedirs.astype(np.float32), "J_regressor": jreg.astype(np.float32),
             "lbs_weights": lbs.astype(np.float32), "parents": parents.astype(np.float32)}
+
+
+# ------------------------------------------------------------------------------------------ HumanAct12 recognition GRU (mld_hip.evaluators.HipActionRecognizer)
+A2M_REC_IN, A2M_REC_H, A2M_REC_L1, A2M_REC_CLASSES = 72, 128, 30, 12
+
+
+def make_a2m_rec_state_dict(seed: int = 12, rec_gain: float = 1.0) -> Dict[str, np.ndarray]:
+    """A seeded stand-in for humanact12_gru.tar's ``model`` (no such file is reachable offline), under its own names (keys without the ``a2m_rec.``
+    prefix): MotionDiscriminator(72, 128, 2, 12) at PyTorch's default init ranges -- U(-1/sqrt(128), +) for every nn.GRU tensor, U(-1/sqrt(fan_in), +) for
+    the Linear weights and biases.  ``rec_gain`` scales the four recurrent weight matrices (3: saturated gates)."""
+    sd: Dict[str, np.ndarray] = {}
+    bound = 1.0 / np.sqrt(A2M_REC_H)
+    for layer, k in ((0, A2M_REC_IN), (1, A2M_REC_H)):
+        for kind, width in (("ih", k), ("hh", A2M_REC_H)):
+            w = f"recurrent.weight_{kind}_l{layer}"
+            sd[w] = (rec_gain * _uniform(seed, w, (3 * A2M_REC_H, width), bound)).astype(np.float32)
+        for kind in ("ih", "hh"):
+            b = f"recurrent.bias_{kind}_l{layer}"
+            sd[b] = _uniform(seed, b, (3 * A2M_REC_H,), bound)
+    _linear(sd, seed, "linear1", A2M_REC_L1, A2M_REC_H)
+    _linear(sd, seed, "linear2", A2M_REC_CLASSES, A2M_REC_L1)
+    return sd
