@@ -164,6 +164,12 @@ typedef struct mldhip_config {
                                  * 1 = the recognition GRU */
   int32_t a2m_max_motions;      /* capacity: motions per mldhip_a2m_recognize call; 0 (default) = 4 x max_batch (one metric update's four passes -- the classifier
                                  * and the FID net on the generated and the ground-truth motions -- in one call) */
+  /* ---- the optional UESTC recognition ST-GCN (mldhip_uestc_recognize below; MLDHIP_ABI_VERSION stays 8: callers detect the feature by the presence of the symbol).
+   * Read only when struct_size covers them (a caller's struct that ends behind a2m_max_motions means no net).  Independent of condition / vae_arch / nfeats.
+   * With uestc_rec = 1 mldhip_create refuses MLDHIP_PREC_BF16. */
+  int32_t uestc_rec;            /* 0 (default) = no net: no weights, no workspace, every uestc_rec.* key accepted and ignored, mis-shaped ones included; 1 = the ST-GCN */
+  int32_t uestc_max_motions;    /* capacity: motions per mldhip_uestc_recognize call; 0 (default) = 2 x max_batch (generated + ground truth in one call) */
+  int32_t uestc_classes;        /* NC, the width of fcn; 0 (default) = 40 (UESTC); 1 .. 256 */
 } mldhip_config;
 
 enum { MLDHIP_COND_TEXT = 0, MLDHIP_COND_ACTION = 1 };
@@ -366,6 +372,9 @@ int mldhip_set_option(mldhip_handle* h, const char* name, int64_t value);
  * split image against fp32 (the embeddings of unit-normal probe rows cannot see a W_hh whose split image lost its precision -- weights near 1e-5, both halves half subnormals
  * -- because the input-side gate terms are O(1) there; a caller's rows may differ): probe_err_eval = the largest max|split - fp32| / max|fp32| of these readings.  FALLBACK: above
  * MLDHIP_PROBE_TOL (or not finite) eval_split_ok = 0 and both towers run their fp32 kernels: results equal MLDHIP_PREC_F32's to the bit.
+ * The UESTC recognition ST-GCN (uestc_rec = 1) is a sixth stage.  PROBE: on an F16X3 handle whose uestc_rec.* group is loaded, finalize runs four seeded motions of
+ * min(16, max_frames) frames (unit-normal rot6d values) on the split-f16 net and on the exact-fp32 net of the same handle: probe_err_uestc = max|split - fp32| / max|fp32|
+ * over features and logits.  FALLBACK: above MLDHIP_PROBE_TOL (or not finite) uestc_split_ok = 0 and the net runs its fp32 GEMMs: results equal MLDHIP_PREC_F32's to the bit.
  * The other modes: F32 has no such limits; BF16 is a reported-only mode whose errors bench.py prints. */
 #define MLDHIP_PROBE_TOL 6e-6f
 #define MLDHIP_PROBE_TOL_HALF 3e-5f
@@ -389,6 +398,9 @@ typedef struct mldhip_numeric_info {
   /* ---- the T2M evaluator towers' stage.  Written only when struct_size covers them (the struct that ends behind probe_err_text is accepted). */
   int32_t eval_split_ok;      /* 1: the evaluator towers multiply on split-f16 MFMAs; 0: fell back to exact fp32, or no evaluators / another mode */
   float probe_err_eval;       /* the evaluator stage's err: the larger of the two towers' (-1: not probed / no evaluators) */
+  /* ---- the UESTC recognition ST-GCN's stage.  Written only when struct_size covers them (the struct that ends behind probe_err_eval is accepted). */
+  int32_t uestc_split_ok;     /* 1: mldhip_uestc_recognize multiplies on split-f16 MFMAs; 0: fell back to exact fp32, or no net / another mode */
+  float probe_err_uestc;      /* that stage's err (-1: not probed / no net) */
 } mldhip_numeric_info;
 /* Synchronises the device (it reads the counter), fills *out and resets nonfinite_values.  No reference counterpart. */
 int mldhip_numeric_status(mldhip_handle* h, mldhip_numeric_info* out);
@@ -750,6 +762,39 @@ int mldhip_smpl_forward(mldhip_handle* h, const float* feats_dev /*[B,T,150]*/, 
  * MLDHIP_ESTATE: no recognizer on the handle, the group not loaded, the handle not finalized. */
 int mldhip_a2m_recognize(mldhip_handle* h, const float* joints_dev /*[B,T,72]*/, const int32_t* lengths_host, const float* h0_dev /*[2,B,128] or NULL = zeros*/,
                          int32_t B, int32_t T, float* logits_out_dev /*[B,12] or NULL*/, float* act_out_dev /*[B,30] or NULL*/, void* stream);
+
+/* The UESTC recognition ST-GCN (handles created with uestc_rec = 1).  Replaces: STGCN(in_channels 6, num_class NC, layout 'smpl', strategy 'spatial',
+ * edge_importance_weighting) of mld/models/architectures/uestc_stgcn.py in eval mode, as UESTCMetrics (mld/models/metrics/stgcn.py) runs it.
+ *
+ * WEIGHTS.  One more optional all-or-nothing group of 149 float32 tensors under the names of uestc_rot6d_stgcn.tar's state dict prefixed uestc_rec. (a wrong shape is
+ * MLDHIP_EINVAL, mldhip_missing_keys reports a half-loaded group; with uestc_rec = 0 every uestc_rec.* key is accepted and ignored; num_batches_tracked is not a tensor
+ * of the group):
+ *   uestc_rec.A [3][24][24] (the checkpoint's registered buffer: no kinematic tree is read at run time);  uestc_rec.data_bn.{weight, bias, running_mean, running_var} [144];
+ *   per block i = 0 .. 9, (Cin -> Cout, stride) = 6 -> 64, 1; 64 -> 64, 1 (x3); 64 -> 128, 2; 128 -> 128, 1 (x2); 128 -> 256, 2; 256 -> 256, 1 (x2):
+ *     uestc_rec.st_gcn_networks.i.gcn.conv.{weight [3 Cout][Cin][1][1], bias [3 Cout]};  .tcn.0.* and .tcn.3.* (BatchNorm: weight, bias, running_mean, running_var [Cout]);
+ *     .tcn.2.{weight [Cout][Cout][9][1], bias [Cout]};  for i = 4, 7 also .residual.0.{weight [Cout][Cin][1][1], bias} and .residual.1.* (BatchNorm);
+ *   uestc_rec.edge_importance.i [3][24][24];  uestc_rec.fcn.{weight [NC][256][1][1], bias [NC]}.
+ *
+ * INPUT.  Element (n, v, c, t) -- motion, joint 0 .. 23, rot6d component 0 .. 5, frame -- is x_dev[n strides[0] + v strides[1] + c strides[2] + t strides[3]]
+ * (elements, all four positive).  MLD's view of feature rows [B][T][150], m.view(B, T, 6, 25).permute(0, 3, 2, 1)[:, :-1], is strides (150 T, 1, 25, 150); a
+ * contiguous [B][24][6][T] tensor is (144 T, 6 T, T, 1).  Neither needs a copy, and both give the same bits.
+ * MATH (eval mode; BatchNorm = the affine of its running statistics, eps 1e-5; dropout = identity).  x <- data_bn over channel v 6 + c.  Then per block:
+ *   y = conv1x1(x) [n][k][Cout][t][v], k = 0 .. 2;  g[n][c][t][w] = sum_k sum_v y[n][k][c][t][v] (A edge_importance[i])[k][v][w];
+ *   h = BN(conv9x1(relu(BN(g)), stride s, padding 4));  out = relu(h + res), res = 0 (block 0), x (Cin = Cout, s = 1) or BN(conv1x1 stride s (x)) (blocks 4, 7);
+ *   T_out = (T - 1) / 2 + 1 at each stride-2 block.  features [256] = the mean of the last block over all (t, v);  logits [NC] = fcn(features).
+ * THERE ARE NO LENGTHS.  The reference has none (it leaves a "TODO: use mask"): all T frames of a motion, padded ones included, enter the convolutions and the
+ * pool.  The engine reproduces that: a caller who wants the reference's numbers passes the padded batch as the reference does.
+ * A motion's outputs do not depend on what else is in the call: bit-identical alone and in any batch (one tile shape, fixed summation orders).  NaN in one
+ * motion stays in that motion.
+ *
+ * KERNELS (kernels/stgcn.hpp; engine/path_uestc.hpp has the folds and the launch order).  ARITHMETIC: MLDHIP_PREC_F32 handles multiply on exact-fp32 MFMAs;
+ * MLDHIP_PREC_F16X3 handles run the GEMMs on split-f16 products while the graph mix, the pool and the head stay fp32 -- the sixth stage of the range contract
+ * above (uestc_split_ok, probe_err_uestc).  Large B runs in chunks sized to the workspace (the numbers do not depend on it).  Stream-ordered, issued eagerly (no
+ * hipGraph); non-finite output values are counted into the sticky counter of mldhip_numeric_status.
+ * MLDHIP_EINVAL: a null input or strides, both outputs NULL, B outside 1 .. uestc_max_motions, T outside 1 .. max_frames, a stride < 1.
+ * MLDHIP_ESTATE: no net on the handle, the group not loaded, the handle not finalized. */
+int mldhip_uestc_recognize(mldhip_handle* h, const float* x_dev, const int64_t strides[4] /* n, v, c, t in elements */, int32_t B, int32_t T,
+                           float* logits_out_dev /*[B,NC] or NULL*/, float* feat_out_dev /*[B,256] or NULL*/, void* stream);
 
 /* Replaces: HumanML3DDataModule.feats2joints (mld/data/HumanML3D.py:41-45 -> recover_from_ric,
  * mld/data/humanml/scripts/motion_process.py:415-432).  feats [B,T,nfeats] -> joints [B,T,njoints,3]. */

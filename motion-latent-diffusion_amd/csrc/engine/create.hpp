@@ -1,7 +1,7 @@
 // Handle construction and teardown: the cluster-lane lock of a device, config validation, the workspace carve of the two variants,
 // the dynamic-LDS registration list, create_engine / destroy_engine.
 // Part of libmldhip's single translation unit (included by ../mldhip.hip, in this order: state, params, dispatch,
-// path_loop, streams, path_vae, path_latent, path_novae, path_clip, path_eval, path_smpl, path_a2m, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace).
+// path_loop, streams, path_vae, path_latent, path_novae, path_clip, path_eval, path_smpl, path_a2m, path_uestc, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace).
 #pragma once
 #if !defined(MLDHIP_SIM)
 #include <fcntl.h>
@@ -138,6 +138,12 @@ const char* config_error(const mldhip_config* cfg) {
   if (cfg->smpl_verts > 0 && cfg->nfeats != 150) return "body model: nfeats must be 150 (25 slots x 6: rot6d of 24 joints + the translation slot)";
   if (cfg->a2m_rec != 0 && cfg->a2m_rec != 1) return "a2m_rec must be 0 (no recognizer) or 1 (the HumanAct12 recognition GRU)";
   if (cfg->a2m_rec && (cfg->a2m_max_motions < 1 || cfg->a2m_max_motions > (1 << 20))) return "recognition GRU: a2m_max_motions must be 1 .. 2^20";
+  if (cfg->uestc_rec != 0 && cfg->uestc_rec != 1) return "uestc_rec must be 0 (no recognizer) or 1 (the UESTC recognition ST-GCN)";
+  if (cfg->uestc_rec) {            // the UESTC recognition ST-GCN (mldhip_uestc_recognize)
+    if (cfg->precision == MLDHIP_PREC_BF16) return "recognition ST-GCN: MLDHIP_PREC_BF16 is refused (exact fp32 or split-f16 only)";
+    if (cfg->uestc_max_motions < 1 || cfg->uestc_max_motions > (1 << 20)) return "recognition ST-GCN: uestc_max_motions must be 1 .. 2^20";
+    if (cfg->uestc_classes < 1 || cfg->uestc_classes > 256) return "recognition ST-GCN: uestc_classes must be 1 .. 256";
+  }
   return nullptr;
 }
 
@@ -240,6 +246,15 @@ void carve_smpl(E* e, Carver& want) {
 void carve_a2m(E* e, Carver& want) {
   if (!e->cfg.a2m_rec) return;
   want(&e->rTab, (size_t)e->cfg.a2m_max_motions);      // ints
+}
+
+// workspace of the UESTC recognition ST-GCN (engine/path_uestc.hpp), carved only when uestc_rec = 1: one chunk of up to kUestcChunk motions at max_frames frames (kUestcWsCap floats at the most)
+void carve_uestc(E* e, Carver& want) {
+  if (!e->cfg.uestc_rec) return;
+  const size_t T = (size_t)e->cfg.max_frames, per = uestc_z_floats((int)T) + 4 * uestc_pad_floats((int)T);
+  const size_t n = std::max<size_t>(1, std::min<size_t>((size_t)std::min(e->cfg.uestc_max_motions, kUestcChunk), kUestcWsCap / per));
+  e->uestc_ws_floats = n * per;
+  want(&e->uZ, e->uestc_ws_floats + 4 * kUestcSlack + 5 * kAlign);      // + the slack rows behind each padded buffer and the five buffers' alignment
 }
 
 // Kernels launched with more dynamic LDS than the default limit register their size once per process and device (tests/test_cabi.py compares this list
@@ -412,6 +427,7 @@ int create_engine(const mldhip_config& cfg, int device, int num_cus, mldhip_hand
   carve_eval(e, want);
   carve_smpl(e, want);
   carve_a2m(e, want);
+  carve_uestc(e, want);
   const size_t Bm = cfg.max_batch;
   e->ws_floats = want.off;
   e->ctxs.resize(cfg.max_in_flight);

@@ -1,6 +1,6 @@
 // Weight contract (SURVEY.md App. B key names), layer binding, scheduler tables, workspace-context plumbing.
 // Part of libmldhip's single translation unit (included by ../mldhip.hip, in this order: state, params, dispatch,
-// path_loop, streams, path_vae, path_latent, path_novae, path_clip, path_eval, path_smpl, path_a2m, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace) except the handle type itself.
+// path_loop, streams, path_vae, path_latent, path_novae, path_clip, path_eval, path_smpl, path_a2m, path_uestc, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace) except the handle type itself.
 #pragma once
 #include <mutex>
 
@@ -142,7 +142,7 @@ size_t add_param(E* e, const std::string& key, std::vector<int64_t> shape) {
   const bool enc = key.rfind("vae.encoder.", 0) == 0 || key.rfind("vae.skel_embedding.", 0) == 0 ||
                    key.rfind("vae.global_motion_token", 0) == 0 || key.rfind("vae.query_pos_encoder.", 0) == 0;
   const bool ev_text = key.rfind("t2m_textencoder.", 0) == 0, ev_motion = !ev_text && (key.rfind("t2m_", 0) == 0 || key == "mean_eval" || key == "std_eval");
-  p.group = key.rfind("a2m_rec.", 0) == 0 ? 8 : key.rfind("smpl.", 0) == 0 ? 7 : ev_text ? 6 : ev_motion ? 5 : key.rfind("denoiser.", 0) == 0 ? 0 : enc ? 3 : key.rfind("vae.", 0) == 0 ? 1 : key.rfind("text_encoder.", 0) == 0 ? 4 : 2;
+  p.group = key.rfind("uestc_rec.", 0) == 0 ? 9 : key.rfind("a2m_rec.", 0) == 0 ? 8 : key.rfind("smpl.", 0) == 0 ? 7 : ev_text ? 6 : ev_motion ? 5 : key.rfind("denoiser.", 0) == 0 ? 0 : enc ? 3 : key.rfind("vae.", 0) == 0 ? 1 : key.rfind("text_encoder.", 0) == 0 ? 4 : 2;
   e->arena_floats += align_up(p.numel);
   e->index[key] = int(e->params.size());
   e->params.push_back(p);
@@ -236,12 +236,36 @@ void declare_a2m_params(E* e) {
   add_param(e, "a2m_rec.linear2.weight", {(int64_t)kA2mCls, (int64_t)kA2mL1}); add_param(e, "a2m_rec.linear2.bias", {(int64_t)kA2mCls});
 }
 
+// The UESTC recognition ST-GCN's 149 tensors (uestc_rec = 1) under the names of uestc_rot6d_stgcn.tar's state dict, prefixed uestc_rec. (shapes as the checkpoint has them)
+void declare_uestc_params(E* e) {
+  const std::string p = "uestc_rec.";
+  const int64_t V = kStgJoints;
+  add_param(e, p + "A", {kStgK, V, V});
+  for (const char* n : {"weight", "bias", "running_mean", "running_var"}) add_param(e, p + "data_bn." + n, {V * kStgIn});
+  auto bn = [&](const std::string& q, int64_t C) { for (const char* n : {"weight", "bias", "running_mean", "running_var"}) add_param(e, q + n, {C}); };
+  for (int i = 0; i < kStgBlocks; ++i) {
+    const int64_t cin = uestc_cin(i), cout = uestc_cout(i);
+    const std::string b = p + "st_gcn_networks." + std::to_string(i) + ".";
+    add_param(e, b + "gcn.conv.weight", {kStgK * cout, cin, 1, 1}); add_param(e, b + "gcn.conv.bias", {kStgK * cout});
+    bn(b + "tcn.0.", cout);
+    add_param(e, b + "tcn.2.weight", {cout, cout, kStgTaps, 1}); add_param(e, b + "tcn.2.bias", {cout});
+    bn(b + "tcn.3.", cout);
+    if (cin != cout && i > 0) {
+      add_param(e, b + "residual.0.weight", {cout, cin, 1, 1}); add_param(e, b + "residual.0.bias", {cout});
+      bn(b + "residual.1.", cout);
+    }
+  }
+  for (int i = 0; i < kStgBlocks; ++i) add_param(e, p + "edge_importance." + std::to_string(i), {kStgK, V, V});
+  add_param(e, p + "fcn.weight", {(int64_t)e->cfg.uestc_classes, kStgFeat, 1, 1}); add_param(e, p + "fcn.bias", {(int64_t)e->cfg.uestc_classes});
+}
+
 void declare_params(E* e) {
   declare_model_params(e);
   if (e->cfg.clip_layers > 0) declare_clip_params(e);
   if (e->cfg.t2m_eval) declare_t2m_params(e);
   if (e->cfg.smpl_verts > 0) declare_smpl_params(e);
   if (e->cfg.a2m_rec) declare_a2m_params(e);
+  if (e->cfg.uestc_rec) declare_uestc_params(e);
 }
 void declare_model_params(E* e) {
   const auto& c = e->cfg;

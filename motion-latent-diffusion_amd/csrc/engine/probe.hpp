@@ -387,6 +387,27 @@ int probe_eval(E* e, hipStream_t stream, ProbeRng& rng) {
   return MLDHIP_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- stage 6: the UESTC recognition ST-GCN
+// four seeded motions of 16 frames (unit-normal rot6d values, what data_bn was fitted to) on the split-f16 net and on the exact-fp32 net of the same handle;
+// err = max |split - fp32| / max |fp32| over features and logits.  One tile shape per mode at every row count: nothing to lift.
+int probe_uestc(E* e, hipStream_t stream, ProbeRng& rng) {
+  const int NB = std::min(4, e->cfg.uestc_max_motions), T = std::min(16, e->cfg.max_frames), NC = e->cfg.uestc_classes;
+  std::vector<float> hx((size_t)NB * kStgJoints * kStgIn * T);
+  rng.fill(hx, 1.0f);
+  ProbeDev x, out;
+  if (x.up(hx) || out.make((size_t)NB * (kStgFeat + NC))) return e->fail(MLDHIP_EHIP, "range probe: hipMalloc");
+  const int64_t strides[4] = {(int64_t)kStgJoints * kStgIn * T, (int64_t)kStgIn * T, T, 1};
+  std::vector<float> ha, hb;
+  for (int split = 1; split >= 0; --split) {
+    e->uestc_split_ok = split != 0;
+    if (int rc = uestc_recognize_impl(e, x.p, strides, NB, T, out.p + (size_t)NB * kStgFeat, out.p, stream, false)) return rc;
+    if (int rc = probe_down(e, stream, out.p, (size_t)NB * (kStgFeat + NC), split ? ha : hb)) return rc;
+  }
+  e->probe_err_uestc = rel_err(ha, hb);
+  e->uestc_split_ok = e->probe_err_uestc <= MLDHIP_PROBE_TOL;
+  return MLDHIP_OK;
+}
+
 int range_probe(E* e, hipStream_t stream, const float* user_text, const float* user_lat, int user_B) {
   Scoped<bool> noise_off(e->noise_off, true);      // deterministic on every handle: the probe compares arithmetic on the eta = 0 step (include/mldhip.h "range_probe")
   ProbeRng rng;
@@ -402,6 +423,8 @@ int range_probe(E* e, hipStream_t stream, const float* user_text, const float* u
     if (int rc = probe_text(e, stream, rng)) return rc;
   if (e->cfg.t2m_eval && (e->group_ready[5] || e->group_ready[6]) && e->arena_x3)
     if (int rc = probe_eval(e, stream, rng)) return rc;
+  if (e->cfg.uestc_rec && e->group_ready[9] && e->uestc_tabs_x3)
+    if (int rc = probe_uestc(e, stream, rng)) return rc;
   e->phase = 0;
   return MLDHIP_OK;
 }

@@ -14,7 +14,7 @@ struct Param {
   size_t numel = 0;
   bool loaded = false;
   int group = 0;       // 0 denoiser, 1 vae decoder, 2 dataset statistics, 3 vae encoder, 4 CLIP text tower, 5 T2M motion evaluators (+ mean_eval / std_eval), 6 T2M text evaluator, 7 SMPL body model,
-                       // 8 HumanAct12 recognition GRU
+                       // 8 HumanAct12 recognition GRU, 9 UESTC recognition ST-GCN
 };
 
 struct EncLayerP {   // TransformerEncoderLayer (cross_attention.py:236-272)
@@ -79,9 +79,9 @@ struct mldhip_engine {
   int device = 0;
   std::string err;
   bool finalized = false;
-  static constexpr int kGroups = 9;
-  bool group_ready[kGroups] = {false, false, false, false, false, false, false, false, false};   // denoiser, vae decoder, mean/std, vae encoder, CLIP text tower (clip_layers > 0), T2M motion / text evaluators (t2m_eval = 1), SMPL body model (smpl_verts > 0),
-                                                                                                 // HumanAct12 recognition GRU (a2m_rec = 1)
+  static constexpr int kGroups = 10;
+  bool group_ready[kGroups] = {false, false, false, false, false, false, false, false, false, false};   // denoiser, vae decoder, mean/std, vae encoder, CLIP text tower (clip_layers > 0), T2M motion / text evaluators (t2m_eval = 1), SMPL body model (smpl_verts > 0),
+                                                                                                 // HumanAct12 recognition GRU (a2m_rec = 1), UESTC recognition ST-GCN (uestc_rec = 1)
 
   // ---- parameters
   std::vector<Param> params;
@@ -115,6 +115,13 @@ struct mldhip_engine {
   float *ev_conv1_w = nullptr, *ev_conv2_w = nullptr, *ev_text_in_w = nullptr, *ev_mbias = nullptr, *ev_tbias = nullptr;   // ... views into it
   float* smpl_tabs = nullptr;     // body model: tables derived from the smpl.* tensors at finalize (engine/path_smpl.hpp) ...
   float *sm_P = nullptr, *sm_W = nullptr, *sm_vt = nullptr, *sm_small = nullptr;   // ... views into it: posedirs / lbs_weights / v_template re-laid per 16-vertex block; J [24][3] | J_i - J_parent(i) [24][3] | parents [24] (ints)
+  // UESTC recognition ST-GCN (uestc_rec = 1; engine/path_uestc.hpp): the tables folded from the uestc_rec.* tensors at finalize (data_bn affine, A * edge_importance per block,
+  // BN-folded GEMM weights padded to K % 128 == 0, per-joint bias tables), the split-f16 image of the same tables (F16X3 handles), and where each block's pieces start
+  float *uestc_tabs = nullptr, *uestc_tabs_x3 = nullptr;
+  struct UestcBlock { int cin = 0, cout = 0, stride = 1, kg = 0, kt = 0, kr = 0; size_t am = 0, gw = 0, gb = 0, tw = 0, tb = 0, rw = 0, rb = 0; };      // offsets in floats; kr = 0: no residual convolution
+  UestcBlock uestc_blk[10];
+  size_t uestc_dbn = 0;           // data_bn scale [144] | offset [144]
+  size_t uestc_ws_floats = 0;     // floats of the workspace that motions may fill (engine/create.hpp carve_uestc): a call's chunk is this over the floats of one motion at its T
   float* arena_x3 = nullptr;  // split-f16 (hi | lo half) image of the arena (precision modes with split-f16 staged GEMMs; built by finalize)
   size_t arena_floats = 0;
   std::vector<EncLayerP> den;      // execution order
@@ -159,6 +166,9 @@ struct mldhip_engine {
   // SMPL body model (smpl_verts > 0; engine/path_smpl.hpp), sized for one chunk of frames: pose features [tiles][208][16], skinning matrices [tiles][12][24][16],
   // per-frame state and translation [frames][4], the call's lengths (ints)
   float *sPf = nullptr, *sA = nullptr, *sAux = nullptr, *sTab = nullptr;
+  // UESTC recognition ST-GCN (uestc_rec = 1; engine/path_uestc.hpp), sized for one chunk of motions: ONE buffer that a call divides by its own T into the compact graph
+  // operand Z, the padded activations Xa / Xb (ping-pong), the graph convolution's output H and the residual convolution's output R
+  float* uZ = nullptr;
   float* rTab = nullptr;      // HumanAct12 recognition GRU (a2m_rec = 1; engine/path_a2m.hpp): the call's lengths (ints, a2m_max_motions of them)
   float* len_rep = nullptr;   // [max_batch] ints: first sample of each sample's length (length_reps_kernel; decoder layer 0 under "dec_lean")
   float* FS = nullptr;   // sample-major loop: parked skip activations [ceil(max_batch / 8)][nb][48][256]
@@ -214,6 +224,8 @@ struct mldhip_engine {
   float probe_err_text = -1.f;   // the tower stage's reading (-1: not probed / no tower)
   bool eval_split_ok = true;     // false: the T2M evaluator towers (engine/path_eval.hpp) run their GEMMs and the recurrence on exact-fp32 MFMAs
   float probe_err_eval = -1.f;   // the evaluator stage's reading (-1: not probed / no evaluators)
+  bool uestc_split_ok = true;    // false: the UESTC recognition ST-GCN (engine/path_uestc.hpp) runs its GEMMs on exact-fp32 MFMAs
+  float probe_err_uestc = -1.f;  // that stage's reading (-1: not probed / no net)
   float probe_err_loop = -1.f, probe_err_decode = -1.f;   // probe results (max-abs difference / max-abs reference); -1: not probed
   unsigned* nonfinite = nullptr; // device counter: non-finite values seen in the latents / joints a sample call produced (sticky until read)
 
@@ -232,7 +244,7 @@ struct mldhip_engine {
   // every device allocation the handle owns outside its contexts: teardown frees what is listed HERE (a new buffer is added beside its declaration, nowhere else)
   std::vector<void**> device_buffers() {
     return {(void**)&arena, (void**)&arena_x3, (void**)&ffn_streams, (void**)&loop_stream, (void**)&loop_stream_x3, (void**)&cl_stream,
-            (void**)&cl_wave_off_dev, (void**)&loop_small, (void**)&trace_buf, (void**)&nonfinite, (void**)&eval_tabs, (void**)&smpl_tabs};
+            (void**)&cl_wave_off_dev, (void**)&loop_small, (void**)&trace_buf, (void**)&nonfinite, (void**)&eval_tabs, (void**)&smpl_tabs, (void**)&uestc_tabs, (void**)&uestc_tabs_x3};
   }
 
   int fail(int code, const char* fmt, ...) {

@@ -12,7 +12,7 @@
 //
 // Source layout: engine/state.hpp (handle, contexts) -> engine/params.hpp (weight contract, schedules) ->
 // engine/dispatch.hpp (kernel selection, the counted launch) -> engine/path_loop.hpp (the latent models' reverse loop) -> engine/streams.hpp (finalize-time weight
-// images) -> engine/path_vae.hpp (VAE decode / encode, feats2joints) -> engine/path_latent.hpp / engine/path_novae.hpp / engine/path_clip.hpp / engine/path_eval.hpp / engine/path_smpl.hpp / engine/path_a2m.hpp (the sample calls, the text tower, the T2M evaluator towers, the SMPL body model, the HumanAct12 recognition GRU) ->
+// images) -> engine/path_vae.hpp (VAE decode / encode, feats2joints) -> engine/path_latent.hpp / engine/path_novae.hpp / engine/path_clip.hpp / engine/path_eval.hpp / engine/path_smpl.hpp / engine/path_a2m.hpp / engine/path_uestc.hpp (the sample calls, the text tower, the T2M evaluator towers, the SMPL body model, the HumanAct12 recognition GRU, the UESTC recognition ST-GCN) ->
 // engine/graphs.hpp (graph capture and caches) -> engine/create.hpp (validation, workspace carve, LDS registration, teardown) ->
 // engine/serve.hpp (the sampling drivers and their shared host sequences) -> engine/probe.hpp (range probe) -> the C ABI below: each
 // entry point is its argument checks and a call into the engine.  kernels/*.hpp hold the device code (no __global__ in this file).
@@ -54,6 +54,7 @@
 #include "kernels/gru.hpp"
 #include "kernels/smpl.hpp"
 #include "kernels/a2m_gru.hpp"
+#include "kernels/stgcn.hpp"
 
 using namespace mld;
 
@@ -69,6 +70,7 @@ using namespace mld;
 #include "engine/path_eval.hpp"
 #include "engine/path_smpl.hpp"
 #include "engine/path_a2m.hpp"
+#include "engine/path_uestc.hpp"
 #include "engine/graphs.hpp"
 #include "engine/create.hpp"
 #include "engine/serve.hpp"
@@ -99,6 +101,7 @@ void mldhip_default_config(mldhip_config* c) {
   c->t2m_eval = 0; c->t2m_max_motions = 0; c->t2m_max_words = 0;
   c->smpl_verts = 0;      // no SMPL body model by default
   c->a2m_rec = 0; c->a2m_max_motions = 0;      // no recognition GRU by default; a2m_max_motions 0 = 4 x max_batch
+  c->uestc_rec = 0; c->uestc_max_motions = 0; c->uestc_classes = 0;      // no recognition ST-GCN by default; uestc_max_motions 0 = 2 x max_batch, uestc_classes 0 = 40
 }
 
 const char* mldhip_last_error(mldhip_handle* h) { return h ? h->err.c_str() : g_last_error.c_str(); }
@@ -114,8 +117,10 @@ int mldhip_create(const mldhip_config* cfg, int device, mldhip_handle** out) {
   constexpr int32_t kCfgNoSmpl = (int32_t)offsetof(mldhip_config, smpl_verts);
   // ... and the a2m_* fields behind smpl_verts: the struct that ends behind smpl_verts means no recognizer
   constexpr int32_t kCfgNoA2m = (int32_t)offsetof(mldhip_config, a2m_rec);
+  // ... and the uestc_* fields behind them: the struct that ends behind a2m_max_motions means no recognition ST-GCN
+  constexpr int32_t kCfgNoUestc = (int32_t)offsetof(mldhip_config, uestc_rec);
   if (cfg->struct_size != (int32_t)sizeof(mldhip_config) && cfg->struct_size != kCfgAbi5 && cfg->struct_size != kCfgAbi6 && cfg->struct_size != kCfgNoEval && cfg->struct_size != kCfgNoSmpl &&
-      cfg->struct_size != kCfgNoA2m) return bad("mldhip_config.struct_size mismatch (ABI skew)");
+      cfg->struct_size != kCfgNoA2m && cfg->struct_size != kCfgNoUestc) return bad("mldhip_config.struct_size mismatch (ABI skew)");
   mldhip_config full;
   mldhip_default_config(&full);                       // fields the caller's struct does not cover keep their defaults ...
   if (cfg->struct_size == kCfgAbi5) full.eta = 0.0f;
@@ -125,6 +130,8 @@ int mldhip_create(const mldhip_config* cfg, int device, mldhip_handle** out) {
   if (full.t2m_eval && full.t2m_max_motions == 0) full.t2m_max_motions = 2 * full.max_batch;
   if (full.t2m_eval && full.t2m_max_words == 0) full.t2m_max_words = 32;
   if (full.a2m_rec && full.a2m_max_motions == 0) full.a2m_max_motions = 4 * full.max_batch;
+  if (full.uestc_rec && full.uestc_max_motions == 0) full.uestc_max_motions = 2 * full.max_batch;
+  if (full.uestc_rec && full.uestc_classes == 0) full.uestc_classes = 40;
   if (const char* what = config_error(&full)) return bad(what);
   int num_cus = 0;
   if (int rc = check_device(device, &num_cus)) return rc;
@@ -143,7 +150,7 @@ int mldhip_load_tensor(mldhip_handle* e, const char* key, const void* data, cons
   auto it = e->index.find(key);
   if (it == e->index.end()) {
     static const char* ignorable[] = {
-                                      "denoiser.mem_pos.", "text_encoder.", "t2m_", "vae.dist_layer.", "smpl.", "a2m_rec."};
+                                      "denoiser.mem_pos.", "text_encoder.", "t2m_", "vae.dist_layer.", "smpl.", "a2m_rec.", "uestc_rec."};
     for (auto p : ignorable)
       if (std::strncmp(key, p, std::strlen(p)) == 0) return 1;
     return e->fail(MLDHIP_EINVAL, "unexpected key %s", key);
@@ -315,6 +322,7 @@ int mldhip_finalize_weights(mldhip_handle* e, void* stream_) {
   if (int rc = build_ffn_streams(c)) return rc;
   if (int rc = build_eval_tables(c)) return rc;
   if (int rc = build_smpl_tables(c)) return rc;
+  if (int rc = build_uestc_tables(c)) return rc;
   for (int k = 0; k < (int)e->ctxs.size(); ++k) {       // the derived tables live in each context's workspace
   bind_context(e, k);
   if (e->group_ready[0]) {
@@ -357,8 +365,8 @@ int mldhip_finalize_weights(mldhip_handle* e, void* stream_) {
   if (e->loop_kernel == 3 && !e->loop_ips)      // (set before finalize: refused here, like mldhip_set_option refuses it afterwards)
     return e->fail(MLDHIP_EINVAL, "loop_kernel 3: the sample-major loop is built for fp32 / split-f16 loop arithmetic, latent_dim 256, ff_size 1024, 4 heads");
   e->finalized = true;
-  e->split_loop_ok = e->split_decode_ok = e->dec_half_ok = e->text_split_ok = e->eval_split_ok = true;
-  e->probe_err_loop = e->probe_err_decode = e->probe_err_decode_half = e->probe_err_text = e->probe_err_eval = -1.f;
+  e->split_loop_ok = e->split_decode_ok = e->dec_half_ok = e->text_split_ok = e->eval_split_ok = e->uestc_split_ok = true;
+  e->probe_err_loop = e->probe_err_decode = e->probe_err_decode_half = e->probe_err_text = e->probe_err_eval = e->probe_err_uestc = -1.f;
   if (e->cfg.precision == MLDHIP_PREC_F16X3 && e->range_probe) {
     if (int rc = range_probe(e, stream)) { e->finalized = false; return rc; }
     e->probe_first_call = e->range_probe == 2;
@@ -371,7 +379,8 @@ int mldhip_numeric_status(mldhip_handle* e, mldhip_numeric_info* out) {
   // ABI 8 appended the text tower's two fields: a caller built against ABI 7 passes the struct that ends behind `reserved` and gets the fields it knows
   // ... and the evaluator towers' two fields came behind them: the struct that ends behind probe_err_text is accepted too
   constexpr int32_t kInfoAbi7 = (int32_t)offsetof(mldhip_numeric_info, text_split_ok), kInfoNoEval = (int32_t)offsetof(mldhip_numeric_info, eval_split_ok);
-  if (out->struct_size != (int32_t)sizeof(mldhip_numeric_info) && out->struct_size != kInfoAbi7 && out->struct_size != kInfoNoEval) return e->fail(MLDHIP_EINVAL, "mldhip_numeric_info.struct_size mismatch (ABI)");
+  constexpr int32_t kInfoNoUestc = (int32_t)offsetof(mldhip_numeric_info, uestc_split_ok);      // ... and the recognition ST-GCN's two behind those
+  if (out->struct_size != (int32_t)sizeof(mldhip_numeric_info) && out->struct_size != kInfoAbi7 && out->struct_size != kInfoNoEval && out->struct_size != kInfoNoUestc) return e->fail(MLDHIP_EINVAL, "mldhip_numeric_info.struct_size mismatch (ABI)");
   DeviceGuard dg(e->device);
   HIP_TRY(e, hipDeviceSynchronize());
   unsigned n = 0;
@@ -380,7 +389,7 @@ int mldhip_numeric_status(mldhip_handle* e, mldhip_numeric_info* out) {
   // a cluster launch that ran into its wait bound poisoned its latents (counted above) and left its status word set: the handle stays off the cluster loop from here on
   // (the captured graphs that hold it are dropped); mldhip_set_option("loop_kernel", 4) re-arms it
   if (!e->cluster_failed && cluster_timed_out(e)) leave_cluster_loop(e);
-  out->probed = e->probe_err_loop >= 0.f || e->probe_err_decode >= 0.f || e->probe_err_text >= 0.f || e->probe_err_eval >= 0.f;
+  out->probed = e->probe_err_loop >= 0.f || e->probe_err_decode >= 0.f || e->probe_err_text >= 0.f || e->probe_err_eval >= 0.f || e->probe_err_uestc >= 0.f;
   out->loop_split_ok = e->cfg.precision == MLDHIP_PREC_F16X3 && e->split_loop_ok;
   out->decode_split_ok = e->cfg.precision == MLDHIP_PREC_F16X3 && e->split_decode_ok;
   out->probe_err_loop = e->probe_err_loop;
@@ -397,6 +406,10 @@ int mldhip_numeric_status(mldhip_handle* e, mldhip_numeric_info* out) {
   if (out->struct_size > kInfoNoEval) {
     out->eval_split_ok = e->cfg.t2m_eval && e->cfg.precision == MLDHIP_PREC_F16X3 && e->arena_x3 && e->eval_split_ok;
     out->probe_err_eval = e->probe_err_eval;
+  }
+  if (out->struct_size > kInfoNoUestc) {
+    out->uestc_split_ok = uestc_x3(e) && e->group_ready[9];
+    out->probe_err_uestc = e->probe_err_uestc;
   }
   return MLDHIP_OK;
 }
@@ -684,6 +697,12 @@ int mldhip_a2m_recognize(mldhip_handle* e, const float* joints_dev, const int32_
   if (!e) return MLDHIP_EINVAL;
   DeviceGuard dg(e->device);
   return a2m_recognize_impl(e, joints_dev, lengths_host, h0_dev, B, T, logits_out_dev, act_out_dev, (hipStream_t)stream_);
+}
+
+int mldhip_uestc_recognize(mldhip_handle* e, const float* x_dev, const int64_t* strides, int32_t B, int32_t T, float* logits_out_dev, float* feat_out_dev, void* stream_) {
+  if (!e) return MLDHIP_EINVAL;
+  DeviceGuard dg(e->device);
+  return uestc_recognize_impl(e, x_dev, strides, B, T, logits_out_dev, feat_out_dev, (hipStream_t)stream_);
 }
 
 int mldhip_feats2joints(mldhip_handle* e, const float* feats_dev, int32_t B, int32_t T, float* joints_out_dev, void* stream_) {

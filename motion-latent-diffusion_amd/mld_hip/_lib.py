@@ -40,6 +40,7 @@ class Config(C.Structure):
         ("t2m_eval", C.c_int32), ("t2m_max_motions", C.c_int32), ("t2m_max_words", C.c_int32),
         ("smpl_verts", C.c_int32),
         ("a2m_rec", C.c_int32), ("a2m_max_motions", C.c_int32),
+        ("uestc_rec", C.c_int32), ("uestc_max_motions", C.c_int32), ("uestc_classes", C.c_int32),
     ]
 
 
@@ -65,7 +66,8 @@ class NumericInfo(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("probed", C.c_int32), ("loop_split_ok", C.c_int32), ("decode_split_ok", C.c_int32),
                 ("probe_err_loop", C.c_float), ("probe_err_decode", C.c_float), ("nonfinite_values", C.c_int64),
                 ("decode_half_ok", C.c_int32), ("probe_err_decode_half", C.c_float), ("cluster_loop", C.c_int32), ("reserved", C.c_int32),
-                ("text_split_ok", C.c_int32), ("probe_err_text", C.c_float), ("eval_split_ok", C.c_int32), ("probe_err_eval", C.c_float)]
+                ("text_split_ok", C.c_int32), ("probe_err_text", C.c_float), ("eval_split_ok", C.c_int32), ("probe_err_eval", C.c_float),
+                ("uestc_split_ok", C.c_int32), ("probe_err_uestc", C.c_float)]
 
 
 PROBE_TOL = 6e-6                         # MLDHIP_PROBE_TOL
@@ -120,6 +122,7 @@ _SYMBOLS = {
     "mldhip_t2m_text_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "mldhip_smpl_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mldhip_a2m_recognize": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mldhip_uestc_recognize": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mldhip_feats2joints": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "mldhip_get_timesteps": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]),
     "mldhip_get_alphas_cumprod": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int32]),
@@ -435,6 +438,15 @@ class Engine:
             raise MldHipError(-2, "this libmldhip has no mldhip_a2m_recognize")
         lens = (C.c_int32 * len(lengths))(*[int(x) for x in lengths])
         self._check(self.lib.mldhip_a2m_recognize(self._h, _ptr(joints), lens, _ptr(h0), len(lengths), int(T), _ptr(logits_out), _ptr(act_out), stream))
+
+    def uestc_recognize(self, x, strides: Sequence[int], B: int, T: int, logits_out=None, feat_out=None, stream: int = 0):
+        """The UESTC recognition ST-GCN (mldhip_uestc_recognize; engines created with uestc_rec=1): ``x`` on the device, element (n, v, c, t) at
+        ``x[n s0 + v s1 + c s2 + t s3]`` with ``strides`` = (s0, s1, s2, s3) in elements (a [B, 24, 6, T] tensor's ``.stride()``), ``logits_out`` [B, NC] and / or
+        ``feat_out`` [B, 256] on the device (None: not stored).  All T frames of every motion are read: the net has no lengths."""
+        if not hasattr(self.lib, "mldhip_uestc_recognize"):
+            raise MldHipError(-2, "this libmldhip has no mldhip_uestc_recognize")
+        st = None if strides is None else (C.c_int64 * 4)(*[int(v) for v in strides])
+        self._check(self.lib.mldhip_uestc_recognize(self._h, _ptr(x), st, int(B), int(T), _ptr(logits_out), _ptr(feat_out), stream))
 
     def feats2joints(self, feats, B: int, T: int, joints_out, stream: int = 0):
         self._check(self.lib.mldhip_feats2joints(self._h, _ptr(feats), B, T, _ptr(joints_out), stream))

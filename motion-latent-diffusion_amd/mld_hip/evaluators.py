@@ -1,4 +1,5 @@
-"""``HipT2MEvaluator`` (below) and ``HipActionRecognizer`` (the HumanAct12 recognition GRU behind mld_hip.metrics.HipHUMANACTMetrics; at the end of this file).
+"""``HipT2MEvaluator`` (below), ``HipActionRecognizer`` (the HumanAct12 recognition GRU behind mld_hip.metrics.HipHUMANACTMetrics) and ``HipStgcnRecognizer``
+(the UESTC recognition ST-GCN behind mld_hip.metrics.HipUESTCMetrics; both at the end of this file).
 
 ``HipT2MEvaluator`` -- the pretrained T2M evaluator nets of a checkpoint (``t2m_moveencoder`` / ``t2m_motionencoder`` / ``t2m_textencoder``:
 mld/models/architectures/t2m_motionenc.py, t2m_textenc.py; instantiated at mld/models/modeltype/mld.py:110-140) as one drop-in module whose arithmetic
@@ -148,3 +149,80 @@ class HipActionRecognizer(HipModule):
         lengths = [T] * B if lengths is None else [int(n) for n in lengths]
         logits, act = self.recognize(self.to_joints(motion_sequence), lengths, hidden_unit.float())
         return act if fid else logits
+
+
+def _find_stgcn_file(path):
+    if not path:
+        return None
+    if os.path.isfile(path):
+        return path
+    f = os.path.join(path, "uestc_rot6d_stgcn.tar")
+    return f if os.path.isfile(f) else None
+
+
+class HipStgcnRecognizer(HipModule):
+    """The pretrained UESTC recognition ST-GCN (``uestc_rot6d_stgcn.tar``: STGCN(in_channels 6, num_class 40, layout 'smpl', strategy 'spatial', edge
+    importance on), mld/models/architectures/uestc_stgcn.py) as one module whose arithmetic runs in libmldhip (``mldhip_uestc_recognize``; include/mldhip.h
+    has the math).  Parameters carry the file's own names (``A``, ``data_bn.weight``, ``st_gcn_networks.0.gcn.conv.weight``, ..., ``fcn.bias``); the
+    ``num_batches_tracked`` scalars of the file are dropped.  ``A`` is the file's registered buffer: no ``kintree_table.pkl`` is read.
+
+    ``uestc_rec_path`` (cfg.model.uestc_rec_path, or the file itself) with a ``uestc_rot6d_stgcn.tar`` in it fills them from the file (the state dict
+    itself, as the reference saves it); otherwise they hold ``mld_hip.synthetic.make_uestc_rec_state_dict`` -- a seeded stand-in, since no such file
+    ships with this repository -- and ``source`` says which; a path that holds no such file gets a ``RuntimeWarning`` saying so.
+
+    THE NET HAS NO LENGTHS (the reference leaves a "TODO: use mask"): every frame of the [B, 24, 6, T] input, padded ones included, counts."""
+    _prefix = "uestc_rec."
+
+    def __init__(self, uestc_rec_path: Optional[str] = None, seed: int = 13, num_class: int = syn.UESTC_CLASSES, tensors: Optional[Dict[str, object]] = None, **_):
+        super().__init__()
+        path = _find_stgcn_file(uestc_rec_path) if tensors is None else None
+        if tensors is not None:
+            self.source = "tensors"
+        elif path is not None:
+            tensors, self.source = torch.load(path, map_location="cpu"), path
+            if "fcn.weight" in tensors:
+                num_class = int(np.shape(tensors["fcn.weight"])[0])
+        else:
+            if uestc_rec_path:
+                warnings.warn(f"HipStgcnRecognizer: no uestc_rot6d_stgcn.tar under uestc_rec_path={uestc_rec_path!r}; the weights are the seeded "
+                              "synthetic stand-in (source == 'synthetic'), so its classes and features are not the pretrained net's", RuntimeWarning, stacklevel=2)
+            tensors, self.source = syn.make_uestc_rec_state_dict(seed, num_class), "synthetic"
+        want = syn.uestc_rec_shapes(num_class)
+        for k, shape in want.items():
+            if k not in tensors or tuple(np.shape(tensors[k])) != shape:
+                raise ValueError(f"HipStgcnRecognizer: {k} {shape} expected (include/mldhip.h)")
+        self.num_class = num_class
+        self._register_tree({k: np.asarray(torch.as_tensor(tensors[k]).float().cpu().numpy(), np.float32) for k in want})      # (num_batches_tracked is not in `want`)
+        # (the config's default 0 MEANS 40: a 40-class net asks for nothing, so it also fits an engine created with the default)
+        self._set_arch("action", uestc_rec=1, **({} if num_class == syn.UESTC_CLASSES else {"uestc_classes": num_class}))
+
+    @staticmethod
+    def capacity(eng) -> int:
+        return int(eng.cfg.uestc_max_motions) or 2 * int(eng.cfg.max_batch)
+
+    @torch.no_grad()
+    def recognize(self, motion: torch.Tensor):
+        """motion: any 4-d float32 [B, 24, 6, T] tensor with positive strides (MLD's view of its feature rows goes in as it is: ``.stride()`` is passed
+        through, nothing is copied) -> (yhat [B, NC], features [B, 256]; [256] at B = 1, the reference's ``squeeze()``); a batch beyond the engine's
+        capacity goes through in slices (a motion's rows do not depend on its neighbours)"""
+        if motion.dim() != 4 or motion.shape[1] != 24 or motion.shape[2] != 6:
+            raise ValueError(f"motion must be [B, 24, 6, T], got {tuple(motion.shape)}")
+        if motion.dtype != torch.float32:
+            raise TypeError(f"motion: float32 expected, got {motion.dtype}")
+        if min(motion.stride()) < 1:
+            motion = motion.contiguous()      # (an expanded dimension has stride 0)
+        B, T = motion.shape[0], motion.shape[3]
+        eng = self.sync_weights()
+        yhat = torch.empty(B, self.num_class, dtype=torch.float32, device=motion.device)
+        feat = torch.empty(B, syn.UESTC_FEAT, dtype=torch.float32, device=motion.device)
+        stream = _engine.current_stream_handle(motion)
+        step = self.capacity(eng)
+        for b0 in range(0, B, step):
+            sl = slice(b0, min(B, b0 + step))
+            eng.uestc_recognize(motion[sl], motion.stride(), sl.stop - b0, T, yhat[sl], feat[sl], stream)
+        return yhat, feat.squeeze()
+
+    def forward(self, motion: torch.Tensor):
+        """STGCN.forward: {'output': motion, 'features': ..., 'yhat': ...}"""
+        yhat, feat = self.recognize(motion)
+        return {"output": motion, "features": feat, "yhat": yhat}

@@ -8,7 +8,10 @@ plain class (torchmetrics is not a dependency): states live on the object, there
 Random draws follow the reference exactly, so under the same seeds the numbers are the reference's:
   * ``update`` draws the four initial states as the reference's four forward calls do -- torch.randn(2, B, 128) on the CPU default generator for the
     classifier on the generated motions, then on the ground truth, then the FID net on each -- and runs them as ONE engine call of 4B motions;
-  * ``compute`` consumes torch.randperm and np.random in the reference's order (the ground-truth diversity / multimodality with the defaults 200 / 20)."""
+  * ``compute`` consumes torch.randperm and np.random in the reference's order (the ground-truth diversity / multimodality with the defaults 200 / 20).
+
+``HipUESTCMetrics`` (at the end of this file) is the same for the reference's UESTCMetrics (mld/models/metrics/stgcn.py; METRIC.TYPE ['UESTCMetrics']) on the
+recognition ST-GCN (``HipStgcnRecognizer``; ``mldhip_uestc_recognize``): the net draws nothing, so ``update`` is one engine call on cat([rec, gt])."""
 from __future__ import annotations
 
 from typing import List, Optional
@@ -18,7 +21,7 @@ import scipy.linalg
 import torch
 from torch import Tensor
 
-from .evaluators import HipActionRecognizer
+from .evaluators import HipActionRecognizer, HipStgcnRecognizer
 
 
 def calculate_activation_statistics(activations: Tensor):
@@ -146,3 +149,35 @@ class HipHUMANACTMetrics:
         self.label_embeddings.append(labels)
         self.recmotion_embeddings.append(act[2 * B:3 * B])
         self.gtmotion_embeddings.append(act[3 * B:])
+
+
+class HipUESTCMetrics(HipHUMANACTMetrics):
+    """A drop-in for UESTCMetrics: ``update(label, recmotion [B, 24, 6, T], gtmotion, lengths)`` / ``compute(sanity_flag)``, the same state names and the
+    eight metric keys.  ``compute`` is HUMANACTMetrics' own -- the reference's two classes share it line for line, the ground-truth diversity call with
+    the helper's default repeat counts included -- on the 256-d features.  ``lengths`` only feed ``count``: the net has no mask (every frame counts, as
+    in the reference)."""
+
+    def __init__(self, datapath: Optional[str] = None, num_labels: int = 40, diversity_times: int = 200, multimodality_times: int = 20,
+                 recognizer: Optional[HipStgcnRecognizer] = None, **kw):
+        """``datapath``: uestc_rot6d_stgcn.tar or the directory holding it (cfg.model.uestc_rec_path).  ``recognizer``: an already built
+        HipStgcnRecognizer (then ``datapath`` is not read).  Other keywords (cfg, dist_sync_on_step, ...) are accepted and ignored."""
+        super().__init__(num_labels=num_labels, diversity_times=diversity_times, multimodality_times=multimodality_times,
+                         recognizer=recognizer if recognizer is not None else HipStgcnRecognizer(datapath, num_class=num_labels))
+
+    @torch.no_grad()
+    def update(self, label: Tensor, recmotion: Tensor, gtmotion: Tensor, lengths: List[int]):
+        self.count += sum(lengths)
+        self.count_seq += len(lengths)
+        labels = label.squeeze().long()
+        B = recmotion.shape[0]
+        yhat, feat = self.recognizer.recognize(torch.cat([recmotion, gtmotion]))      # generated + ground truth: one engine call
+        feat = feat.reshape(2 * B, -1)
+        batch_pred = yhat[:B].max(dim=1).indices.cpu()
+        gt_batch_pred = yhat[B:].max(dim=1).indices.cpu()
+        for lab, pred in zip(labels.cpu().reshape(-1), batch_pred):
+            self.confusion[lab][pred] += 1
+        for lab, pred in zip(labels.cpu().reshape(-1), gt_batch_pred):
+            self.gt_confusion[lab][pred] += 1
+        self.label_embeddings.append(labels)
+        self.recmotion_embeddings.append(feat[:B].squeeze())
+        self.gtmotion_embeddings.append(feat[B:].squeeze())

@@ -413,3 +413,97 @@ def make_a2m_rec_state_dict(seed: int = 12, rec_gain: float = 1.0) -> Dict[str, 
     _linear(sd, seed, "linear1", A2M_REC_L1, A2M_REC_H)
     _linear(sd, seed, "linear2", A2M_REC_CLASSES, A2M_REC_L1)
     return sd
+
+
+# ------------------------------------------------------------------------------------------ UESTC recognition ST-GCN (mld_hip.evaluators.HipStgcnRecognizer)
+UESTC_JOINTS, UESTC_IN, UESTC_FEAT, UESTC_CLASSES = 24, 6, 256, 40
+UESTC_BLOCKS = ((6, 64, 1), (64, 64, 1), (64, 64, 1), (64, 64, 1), (64, 128, 2), (128, 128, 1), (128, 128, 1), (128, 256, 2), (256, 256, 1), (256, 256, 1))
+
+
+def uestc_graph(parents: Tuple[int, ...] = SMPL_PARENTS) -> np.ndarray:
+    """A [3, 24, 24] of the ST-GCN's spatial partitioning on the SMPL tree, restated: joints j and i are linked when their hop distance is <= 1 (a
+    joint, its parent and its children); the 0/1 link matrix is column-normalised (entry [j, i] over the link count of column i).  Slice 0 holds the
+    self links.  A link between different joints goes by the distance of both ends to joint 0, known only up to 1 hop (0 for the root, 1 for its
+    children, unknown = infinite beyond): equal distances -> slice 1 (the 'root' group), j further than i -> slice 1 too (the 'closer' group is
+    added to it), j nearer than i -> slice 2 ('further')."""
+    n = len(parents)
+    link = np.eye(n)
+    for j, p in enumerate(parents):
+        if p >= 0:
+            link[j, p] = link[p, j] = 1.0
+    norm = link / link.sum(axis=0, keepdims=True)
+    dist = np.full(n, np.inf)
+    dist[0] = 0.0
+    dist[[j for j, p in enumerate(parents) if p == 0]] = 1.0
+    A = np.zeros((3, n, n))
+    for i in range(n):
+        for j in range(n):
+            if not link[j, i]:
+                continue
+            if i == j:
+                A[0, j, i] = norm[j, i]
+            elif dist[j] >= dist[i]:
+                A[1, j, i] = norm[j, i]
+            else:
+                A[2, j, i] = norm[j, i]
+    return A.astype(np.float32)
+
+
+def uestc_rec_shapes(num_class: int = UESTC_CLASSES) -> Dict[str, Tuple[int, ...]]:
+    """{key: shape} of the 149 tensors of the group (keys without the ``uestc_rec.`` prefix), as the checkpoint has them"""
+    V = UESTC_JOINTS
+    sh: Dict[str, Tuple[int, ...]] = {"A": (3, V, V)}
+
+    def bn(prefix, c):
+        for n in ("weight", "bias", "running_mean", "running_var"):
+            sh[f"{prefix}.{n}"] = (c,)
+
+    bn("data_bn", V * UESTC_IN)
+    for i, (cin, cout, _) in enumerate(UESTC_BLOCKS):
+        p = f"st_gcn_networks.{i}"
+        sh[f"{p}.gcn.conv.weight"], sh[f"{p}.gcn.conv.bias"] = (3 * cout, cin, 1, 1), (3 * cout,)
+        bn(f"{p}.tcn.0", cout)
+        sh[f"{p}.tcn.2.weight"], sh[f"{p}.tcn.2.bias"] = (cout, cout, 9, 1), (cout,)
+        bn(f"{p}.tcn.3", cout)
+        if i > 0 and cin != cout:
+            sh[f"{p}.residual.0.weight"], sh[f"{p}.residual.0.bias"] = (cout, cin, 1, 1), (cout,)
+            bn(f"{p}.residual.1", cout)
+    for i in range(len(UESTC_BLOCKS)):
+        sh[f"edge_importance.{i}"] = (3, V, V)
+    sh["fcn.weight"], sh["fcn.bias"] = (num_class, UESTC_FEAT, 1, 1), (num_class,)
+    return sh
+
+
+def make_uestc_rec_state_dict(seed: int = 13, num_class: int = UESTC_CLASSES, bn_gain: float = 1.0, in_gain: float = 1.0) -> Dict[str, np.ndarray]:
+    """A seeded stand-in for uestc_rot6d_stgcn.tar (no such file is reachable offline), under its own names (keys without the ``uestc_rec.`` prefix; 149
+    tensors, the ``num_batches_tracked`` scalars left out): ``A`` from ``uestc_graph``; convolutions at PyTorch's default init range U(-1/sqrt(fan_in), +);
+    BatchNorm statistics, gammas, betas and the edge importances seeded AWAY from the identity (running_var in [0.5, 2], gamma in [0.5, 1.5], beta and
+    running_mean in [-0.2, 0.2], importance in [0.5, 1.5]) so that every fold the engine makes at finalize changes the numbers.  ``bn_gain`` multiplies
+    every block's gammas (2: activations that grow with depth); ``in_gain`` multiplies data_bn's gamma and beta (1e6: inputs far outside the half range)."""
+    sd: Dict[str, np.ndarray] = {"A": uestc_graph()}
+
+    def bn(prefix, c, gain=1.0):
+        sd[f"{prefix}.weight"] = (gain * (1.0 + _uniform(seed, f"{prefix}.weight", (c,), 0.5))).astype(np.float32)
+        sd[f"{prefix}.bias"] = ((gain if prefix == "data_bn" else 1.0) * _uniform(seed, f"{prefix}.bias", (c,), 0.2)).astype(np.float32)
+        sd[f"{prefix}.running_mean"] = _uniform(seed, f"{prefix}.running_mean", (c,), 0.2)
+        sd[f"{prefix}.running_var"] = (1.25 + _uniform(seed, f"{prefix}.running_var", (c,), 0.75)).astype(np.float32)
+
+    def conv(prefix, shape):
+        bound = 1.0 / np.sqrt(shape[1] * shape[2])
+        sd[f"{prefix}.weight"] = _uniform(seed, f"{prefix}.weight", shape, bound)
+        sd[f"{prefix}.bias"] = _uniform(seed, f"{prefix}.bias", (shape[0],), bound)
+
+    bn("data_bn", UESTC_JOINTS * UESTC_IN, in_gain)
+    for i, (cin, cout, _) in enumerate(UESTC_BLOCKS):
+        p = f"st_gcn_networks.{i}"
+        conv(f"{p}.gcn.conv", (3 * cout, cin, 1, 1))
+        bn(f"{p}.tcn.0", cout, bn_gain)
+        conv(f"{p}.tcn.2", (cout, cout, 9, 1))
+        bn(f"{p}.tcn.3", cout, bn_gain)
+        if i > 0 and cin != cout:
+            conv(f"{p}.residual.0", (cout, cin, 1, 1))
+            bn(f"{p}.residual.1", cout)
+    for i in range(len(UESTC_BLOCKS)):
+        sd[f"edge_importance.{i}"] = (1.0 + _uniform(seed, f"edge_importance.{i}", (3, UESTC_JOINTS, UESTC_JOINTS), 0.5)).astype(np.float32)
+    conv("fcn", (num_class, UESTC_FEAT, 1, 1))
+    return sd
