@@ -170,6 +170,13 @@ typedef struct mldhip_config {
   int32_t uestc_rec;            /* 0 (default) = no net: no weights, no workspace, every uestc_rec.* key accepted and ignored, mis-shaped ones included; 1 = the ST-GCN */
   int32_t uestc_max_motions;    /* capacity: motions per mldhip_uestc_recognize call; 0 (default) = 2 x max_batch (generated + ground truth in one call) */
   int32_t uestc_classes;        /* NC, the width of fcn; 0 (default) = 40 (UESTC); 1 .. 256 */
+  /* ---- the optional text-to-motion metric kernels (mldhip_t2m_match / mldhip_act_stats / mldhip_pair_dist below; MLDHIP_ABI_VERSION stays 8: callers detect the
+   * feature by the presence of the symbols).  Read only when struct_size covers them (a caller's struct that ends behind uestc_classes means no metrics).
+   * Independent of every other field (condition, vae_arch, nfeats, precision); there are no weights, and the calls work before and after mldhip_finalize_weights. */
+  int32_t t2m_metrics;          /* 0 (default) = none: no workspace; 1 = the three calls */
+  int32_t metrics_max_rows;     /* capacity: N (rows) and P (pairs) of a call; 0 (default) = 8192; 2 .. 2^20.
+                                 * WORKSPACE: 2 x metrics_max_rows 32-bit words per context (the a | b index tables of mldhip_pair_dist) and nothing else:
+                                 * the statistics keep their chunk sums in registers. */
 } mldhip_config;
 
 enum { MLDHIP_COND_TEXT = 0, MLDHIP_COND_ACTION = 1 };
@@ -795,6 +802,40 @@ int mldhip_a2m_recognize(mldhip_handle* h, const float* joints_dev /*[B,T,72]*/,
  * MLDHIP_ESTATE: no net on the handle, the group not loaded, the handle not finalized. */
 int mldhip_uestc_recognize(mldhip_handle* h, const float* x_dev, const int64_t strides[4] /* n, v, c, t in elements */, int32_t B, int32_t T,
                            float* logits_out_dev /*[B,NC] or NULL*/, float* feat_out_dev /*[B,256] or NULL*/, void* stream);
+
+/* The text-to-motion metric kernels (handles created with t2m_metrics = 1): the device-shaped parts of TM2TMetrics (mld/models/metrics/tm2t.py) and MMMetrics
+ * (mm.py) -- grouped retrieval, activation statistics, pair distances -- on embeddings that stay on the device.  The matrix square root of the FID and
+ * the random draws stay with the caller (mld_hip.metrics.HipTM2TMetrics / HipMMMetrics).
+ *
+ * COMMON RULES.  1 <= D <= 1024; rows are dense (row stride D).  Stream-ordered, issued eagerly (no hipGraph).  ARITHMETIC: exact fp32 in EVERY precision mode
+ * (v_mfma_f32_16x16x4_f32 for the products, fp32 VALU elsewhere; no stage of the range contract): an MLDHIP_PREC_F16X3 or MLDHIP_PREC_BF16 handle gives the
+ * bits of an MLDHIP_PREC_F32 one -- ranks are discrete and the FID goes through a matrix square root.  Summation order is fixed and there are no atomics:
+ * results are bit-identical from call to call and do not depend on metrics_max_rows, on the grid or on what else runs.
+ * MLDHIP_EINVAL: a null required pointer, a size out of range, N > metrics_max_rows, P outside 1 .. metrics_max_rows, an index outside 0 .. N - 1 (checked on
+ * the host before anything is launched), both outputs NULL in mldhip_t2m_match.  MLDHIP_ESTATE: the handle was created with t2m_metrics = 0.
+ *
+ * mldhip_t2m_match.  Replaces one pass of the group loop of TM2TMetrics.compute (tm2t.py:100-113, :122-134: euclidean_distance_matrix, .nan_to_num(), .trace(),
+ * argsort, calculate_top_k).  1 <= R <= 32, G = N / R (integer division; the last N - G R rows are ignored and their outputs left untouched, as in the
+ * reference).  For group g and rows i, j of it:  d[i][j] = sqrt((-2 t_i.m_j + |t_i|^2) + |m_j|^2)  (the reference's expansion, in its order); a negative or NaN
+ * argument of the root gives 0 (what nan_to_num makes of it), +inf becomes FLT_MAX.  diag[g R + i] = d[i][i];  rank[g R + i] = #{j : d[i][j] < d[i][i]} +
+ * #{j < i : d[i][j] == d[i][i]}, the position a stable ascending sort gives column i.  The caller derives the top-k hit as rank < k and the matching score
+ * as the sum of diag.  KERNEL (kernels/t2m_metrics.hpp): one workgroup per group; the group is one 32 x 32 accumulator tile (four 16 x 16 MFMA tiles, one
+ * per wave), rows behind R and columns behind D are zeros (K is padded to the instruction's 4).
+ *
+ * mldhip_act_stats.  Replaces calculate_activation_statistics_np (np.mean(axis=0), np.cov(rowvar=False)).  N >= 2.  mean[d] = column mean;
+ * cov = (X - mean)^T (X - mean) / (N - 1): rows are centred BEFORE they are multiplied (two passes; no E[xx] - E[x]E[x] form).  The row sum is two-level:
+ * chunks of MLDHIP_ACT_STATS_CHUNK rows (the last one shorter), each summed from zero, the chunk sums added in ascending order.  cov is exactly symmetric:
+ * only elements i <= j are computed, each is stored to [i][j] and [j][i].
+ *
+ * mldhip_pair_dist.  Replaces the distance part of calculate_diversity_np / calculate_multimodality_np: dist[p] = sqrt(sum_d (x[a[p]][d] - x[b[p]][d])^2), the
+ * difference form (a == b gives exactly 0).  One wave per pair.  The index tables reach the kernel through an engine-owned table uploaded with the call. */
+#define MLDHIP_ACT_STATS_CHUNK 256
+int mldhip_t2m_match(mldhip_handle* h, const float* text_dev /*[N][D]*/, const float* motion_dev /*[N][D]*/, int32_t N, int32_t D, int32_t R,
+                     int32_t* rank_out_dev /*[G*R] or NULL*/, float* diag_out_dev /*[G*R] or NULL*/, void* stream);
+int mldhip_act_stats(mldhip_handle* h, const float* x_dev /*[N][D]*/, int32_t N, int32_t D, float* mean_out_dev /*[D]*/, float* cov_out_dev /*[D][D]*/,
+                     void* stream);
+int mldhip_pair_dist(mldhip_handle* h, const float* x_dev /*[N][D]*/, int32_t N, int32_t D, const int32_t* a_host /*[P]*/, const int32_t* b_host /*[P]*/,
+                     int32_t P, float* dist_out_dev /*[P]*/, void* stream);
 
 /* Replaces: HumanML3DDataModule.feats2joints (mld/data/HumanML3D.py:41-45 -> recover_from_ric,
  * mld/data/humanml/scripts/motion_process.py:415-432).  feats [B,T,nfeats] -> joints [B,T,njoints,3]. */

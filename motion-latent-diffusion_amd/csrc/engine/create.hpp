@@ -1,7 +1,7 @@
 // Handle construction and teardown: the cluster-lane lock of a device, config validation, the workspace carve of the two variants,
 // the dynamic-LDS registration list, create_engine / destroy_engine.
 // Part of libmldhip's single translation unit (included by ../mldhip.hip, in this order: state, params, dispatch,
-// path_loop, streams, path_vae, path_latent, path_novae, path_clip, path_eval, path_smpl, path_a2m, path_uestc, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace).
+// path_loop, streams, path_vae, path_latent, path_novae, path_clip, path_eval, path_smpl, path_a2m, path_uestc, path_metrics, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace).
 #pragma once
 #if !defined(MLDHIP_SIM)
 #include <fcntl.h>
@@ -144,6 +144,8 @@ const char* config_error(const mldhip_config* cfg) {
     if (cfg->uestc_max_motions < 1 || cfg->uestc_max_motions > (1 << 20)) return "recognition ST-GCN: uestc_max_motions must be 1 .. 2^20";
     if (cfg->uestc_classes < 1 || cfg->uestc_classes > 256) return "recognition ST-GCN: uestc_classes must be 1 .. 256";
   }
+  if (cfg->t2m_metrics != 0 && cfg->t2m_metrics != 1) return "t2m_metrics must be 0 (no metric kernels) or 1 (mldhip_t2m_match / mldhip_act_stats / mldhip_pair_dist)";
+  if (cfg->t2m_metrics && (cfg->metrics_max_rows < 2 || cfg->metrics_max_rows > (1 << 20))) return "metric kernels: metrics_max_rows must be 2 .. 2^20";
   return nullptr;
 }
 
@@ -255,6 +257,12 @@ void carve_uestc(E* e, Carver& want) {
   const size_t n = std::max<size_t>(1, std::min<size_t>((size_t)std::min(e->cfg.uestc_max_motions, kUestcChunk), kUestcWsCap / per));
   e->uestc_ws_floats = n * per;
   want(&e->uZ, e->uestc_ws_floats + 4 * kUestcSlack + 5 * kAlign);      // + the slack rows behind each padded buffer and the five buffers' alignment
+}
+
+// workspace of the text-to-motion metric kernels (engine/path_metrics.hpp), carved only when t2m_metrics = 1: the a | b index tables of mldhip_pair_dist
+void carve_metrics(E* e, Carver& want) {
+  if (!e->cfg.t2m_metrics) return;
+  want(&e->mTab, 2 * (size_t)e->cfg.metrics_max_rows);      // ints
 }
 
 // Kernels launched with more dynamic LDS than the default limit register their size once per process and device (tests/test_cabi.py compares this list
@@ -428,6 +436,7 @@ int create_engine(const mldhip_config& cfg, int device, int num_cus, mldhip_hand
   carve_smpl(e, want);
   carve_a2m(e, want);
   carve_uestc(e, want);
+  carve_metrics(e, want);
   const size_t Bm = cfg.max_batch;
   e->ws_floats = want.off;
   e->ctxs.resize(cfg.max_in_flight);

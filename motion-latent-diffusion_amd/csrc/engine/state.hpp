@@ -59,6 +59,7 @@ struct WsContext {
   std::vector<int32_t> eval_tab_host;  // evaluator towers: stable host copy of the call's length tables (engine/path_eval.hpp)
   std::vector<int32_t> smpl_tab_host;  // body model: stable host copy of the call's lengths (engine/path_smpl.hpp)
   std::vector<int32_t> a2m_tab_host;   // recognition GRU: stable host copy of the call's lengths (engine/path_a2m.hpp)
+  std::vector<int32_t> met_tab_host;   // metric kernels: stable host copy of the call's a | b index tables (engine/path_metrics.hpp)
   bool used = false;
   unsigned long long seed_host = 0;   // stable host copy of the Philox seed while it is uploaded to seed_slot
 #if !defined(MLDHIP_SIM)
@@ -169,6 +170,7 @@ struct mldhip_engine {
   // UESTC recognition ST-GCN (uestc_rec = 1; engine/path_uestc.hpp), sized for one chunk of motions: ONE buffer that a call divides by its own T into the compact graph
   // operand Z, the padded activations Xa / Xb (ping-pong), the graph convolution's output H and the residual convolution's output R
   float* uZ = nullptr;
+  float* mTab = nullptr;      // text-to-motion metric kernels (t2m_metrics = 1; engine/path_metrics.hpp): the a | b index tables of mldhip_pair_dist (ints, 2 x metrics_max_rows of them)
   float* rTab = nullptr;      // HumanAct12 recognition GRU (a2m_rec = 1; engine/path_a2m.hpp): the call's lengths (ints, a2m_max_motions of them)
   float* len_rep = nullptr;   // [max_batch] ints: first sample of each sample's length (length_reps_kernel; decoder layer 0 under "dec_lean")
   float* FS = nullptr;   // sample-major loop: parked skip activations [ceil(max_batch / 8)][nb][48][256]

@@ -12,7 +12,7 @@
 //
 // Source layout: engine/state.hpp (handle, contexts) -> engine/params.hpp (weight contract, schedules) ->
 // engine/dispatch.hpp (kernel selection, the counted launch) -> engine/path_loop.hpp (the latent models' reverse loop) -> engine/streams.hpp (finalize-time weight
-// images) -> engine/path_vae.hpp (VAE decode / encode, feats2joints) -> engine/path_latent.hpp / engine/path_novae.hpp / engine/path_clip.hpp / engine/path_eval.hpp / engine/path_smpl.hpp / engine/path_a2m.hpp / engine/path_uestc.hpp (the sample calls, the text tower, the T2M evaluator towers, the SMPL body model, the HumanAct12 recognition GRU, the UESTC recognition ST-GCN) ->
+// images) -> engine/path_vae.hpp (VAE decode / encode, feats2joints) -> engine/path_latent.hpp / engine/path_novae.hpp / engine/path_clip.hpp / engine/path_eval.hpp / engine/path_smpl.hpp / engine/path_a2m.hpp / engine/path_uestc.hpp / engine/path_metrics.hpp (the sample calls, the text tower, the T2M evaluator towers, the SMPL body model, the HumanAct12 recognition GRU, the UESTC recognition ST-GCN, the text-to-motion metric kernels) ->
 // engine/graphs.hpp (graph capture and caches) -> engine/create.hpp (validation, workspace carve, LDS registration, teardown) ->
 // engine/serve.hpp (the sampling drivers and their shared host sequences) -> engine/probe.hpp (range probe) -> the C ABI below: each
 // entry point is its argument checks and a call into the engine.  kernels/*.hpp hold the device code (no __global__ in this file).
@@ -55,6 +55,7 @@
 #include "kernels/smpl.hpp"
 #include "kernels/a2m_gru.hpp"
 #include "kernels/stgcn.hpp"
+#include "kernels/t2m_metrics.hpp"
 
 using namespace mld;
 
@@ -71,6 +72,7 @@ using namespace mld;
 #include "engine/path_smpl.hpp"
 #include "engine/path_a2m.hpp"
 #include "engine/path_uestc.hpp"
+#include "engine/path_metrics.hpp"
 #include "engine/graphs.hpp"
 #include "engine/create.hpp"
 #include "engine/serve.hpp"
@@ -102,6 +104,7 @@ void mldhip_default_config(mldhip_config* c) {
   c->smpl_verts = 0;      // no SMPL body model by default
   c->a2m_rec = 0; c->a2m_max_motions = 0;      // no recognition GRU by default; a2m_max_motions 0 = 4 x max_batch
   c->uestc_rec = 0; c->uestc_max_motions = 0; c->uestc_classes = 0;      // no recognition ST-GCN by default; uestc_max_motions 0 = 2 x max_batch, uestc_classes 0 = 40
+  c->t2m_metrics = 0; c->metrics_max_rows = 0;      // no metric kernels by default; metrics_max_rows 0 = 8192
 }
 
 const char* mldhip_last_error(mldhip_handle* h) { return h ? h->err.c_str() : g_last_error.c_str(); }
@@ -119,8 +122,10 @@ int mldhip_create(const mldhip_config* cfg, int device, mldhip_handle** out) {
   constexpr int32_t kCfgNoA2m = (int32_t)offsetof(mldhip_config, a2m_rec);
   // ... and the uestc_* fields behind them: the struct that ends behind a2m_max_motions means no recognition ST-GCN
   constexpr int32_t kCfgNoUestc = (int32_t)offsetof(mldhip_config, uestc_rec);
+  // ... and the two metric fields behind those: the struct that ends behind uestc_classes means no metric kernels
+  constexpr int32_t kCfgNoMetrics = (int32_t)offsetof(mldhip_config, t2m_metrics);
   if (cfg->struct_size != (int32_t)sizeof(mldhip_config) && cfg->struct_size != kCfgAbi5 && cfg->struct_size != kCfgAbi6 && cfg->struct_size != kCfgNoEval && cfg->struct_size != kCfgNoSmpl &&
-      cfg->struct_size != kCfgNoA2m && cfg->struct_size != kCfgNoUestc) return bad("mldhip_config.struct_size mismatch (ABI skew)");
+      cfg->struct_size != kCfgNoA2m && cfg->struct_size != kCfgNoUestc && cfg->struct_size != kCfgNoMetrics) return bad("mldhip_config.struct_size mismatch (ABI skew)");
   mldhip_config full;
   mldhip_default_config(&full);                       // fields the caller's struct does not cover keep their defaults ...
   if (cfg->struct_size == kCfgAbi5) full.eta = 0.0f;
@@ -132,6 +137,7 @@ int mldhip_create(const mldhip_config* cfg, int device, mldhip_handle** out) {
   if (full.a2m_rec && full.a2m_max_motions == 0) full.a2m_max_motions = 4 * full.max_batch;
   if (full.uestc_rec && full.uestc_max_motions == 0) full.uestc_max_motions = 2 * full.max_batch;
   if (full.uestc_rec && full.uestc_classes == 0) full.uestc_classes = 40;
+  if (full.t2m_metrics && full.metrics_max_rows == 0) full.metrics_max_rows = 8192;
   if (const char* what = config_error(&full)) return bad(what);
   int num_cus = 0;
   if (int rc = check_device(device, &num_cus)) return rc;
@@ -703,6 +709,26 @@ int mldhip_uestc_recognize(mldhip_handle* e, const float* x_dev, const int64_t* 
   if (!e) return MLDHIP_EINVAL;
   DeviceGuard dg(e->device);
   return uestc_recognize_impl(e, x_dev, strides, B, T, logits_out_dev, feat_out_dev, (hipStream_t)stream_);
+}
+
+int mldhip_t2m_match(mldhip_handle* e, const float* text_dev, const float* motion_dev, int32_t N, int32_t D, int32_t R, int32_t* rank_out_dev, float* diag_out_dev,
+                     void* stream_) {
+  if (!e) return MLDHIP_EINVAL;
+  DeviceGuard dg(e->device);
+  return t2m_match_impl(e, text_dev, motion_dev, N, D, R, rank_out_dev, diag_out_dev, (hipStream_t)stream_);
+}
+
+int mldhip_act_stats(mldhip_handle* e, const float* x_dev, int32_t N, int32_t D, float* mean_out_dev, float* cov_out_dev, void* stream_) {
+  if (!e) return MLDHIP_EINVAL;
+  DeviceGuard dg(e->device);
+  return act_stats_impl(e, x_dev, N, D, mean_out_dev, cov_out_dev, (hipStream_t)stream_);
+}
+
+int mldhip_pair_dist(mldhip_handle* e, const float* x_dev, int32_t N, int32_t D, const int32_t* a_host, const int32_t* b_host, int32_t P, float* dist_out_dev,
+                     void* stream_) {
+  if (!e) return MLDHIP_EINVAL;
+  DeviceGuard dg(e->device);
+  return pair_dist_impl(e, x_dev, N, D, a_host, b_host, P, dist_out_dev, (hipStream_t)stream_);
 }
 
 int mldhip_feats2joints(mldhip_handle* e, const float* feats_dev, int32_t B, int32_t T, float* joints_out_dev, void* stream_) {

@@ -41,6 +41,7 @@ class Config(C.Structure):
         ("smpl_verts", C.c_int32),
         ("a2m_rec", C.c_int32), ("a2m_max_motions", C.c_int32),
         ("uestc_rec", C.c_int32), ("uestc_max_motions", C.c_int32), ("uestc_classes", C.c_int32),
+        ("t2m_metrics", C.c_int32), ("metrics_max_rows", C.c_int32),
     ]
 
 
@@ -123,6 +124,9 @@ _SYMBOLS = {
     "mldhip_smpl_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mldhip_a2m_recognize": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mldhip_uestc_recognize": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mldhip_t2m_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mldhip_act_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mldhip_pair_dist": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_void_p]),
     "mldhip_feats2joints": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "mldhip_get_timesteps": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]),
     "mldhip_get_alphas_cumprod": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int32]),
@@ -447,6 +451,24 @@ class Engine:
             raise MldHipError(-2, "this libmldhip has no mldhip_uestc_recognize")
         st = None if strides is None else (C.c_int64 * 4)(*[int(v) for v in strides])
         self._check(self.lib.mldhip_uestc_recognize(self._h, _ptr(x), st, int(B), int(T), _ptr(logits_out), _ptr(feat_out), stream))
+
+    def t2m_match(self, text, motion, N: int, D: int, R: int, rank_out=None, diag_out=None, stream: int = 0):
+        """Grouped retrieval (mldhip_t2m_match; engines created with t2m_metrics=1): ``text`` / ``motion`` [N, D] float32 on the device, groups of ``R`` rows;
+        ``rank_out`` [N // R * R] int32 and / or ``diag_out`` [N // R * R] float32 on the device (None: not stored)."""
+        self._check(self.lib.mldhip_t2m_match(self._h, _ptr(text), _ptr(motion), int(N), int(D), int(R), _ptr(rank_out), _ptr(diag_out), stream))
+
+    def act_stats(self, x, N: int, D: int, mean_out, cov_out, stream: int = 0):
+        """Mean [D] and unbiased covariance [D, D] of ``x`` [N, D] (mldhip_act_stats), all float32 on the device."""
+        self._check(self.lib.mldhip_act_stats(self._h, _ptr(x), int(N), int(D), _ptr(mean_out), _ptr(cov_out), stream))
+
+    def pair_dist(self, x, N: int, D: int, a: Sequence[int], b: Sequence[int], dist_out, stream: int = 0):
+        """``dist_out[p] = ||x[a[p]] - x[b[p]]||`` (mldhip_pair_dist): ``x`` [N, D] and ``dist_out`` [P] float32 on the device, ``a`` / ``b`` [P] on the host."""
+        if len(a) != len(b):
+            raise ValueError("one b per a")
+        ia = np.ascontiguousarray(a, dtype=np.int32)
+        ib = np.ascontiguousarray(b, dtype=np.int32)
+        i32p = C.POINTER(C.c_int32)
+        self._check(self.lib.mldhip_pair_dist(self._h, _ptr(x), int(N), int(D), ia.ctypes.data_as(i32p), ib.ctypes.data_as(i32p), len(ia), _ptr(dist_out), stream))
 
     def feats2joints(self, feats, B: int, T: int, joints_out, stream: int = 0):
         self._check(self.lib.mldhip_feats2joints(self._h, _ptr(feats), B, T, _ptr(joints_out), stream))

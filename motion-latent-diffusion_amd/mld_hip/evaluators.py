@@ -1,5 +1,6 @@
 """``HipT2MEvaluator`` (below), ``HipActionRecognizer`` (the HumanAct12 recognition GRU behind mld_hip.metrics.HipHUMANACTMetrics) and ``HipStgcnRecognizer``
-(the UESTC recognition ST-GCN behind mld_hip.metrics.HipUESTCMetrics; both at the end of this file).
+(the UESTC recognition ST-GCN behind mld_hip.metrics.HipUESTCMetrics; both behind it), and ``HipMetricOps`` (the metric kernels behind
+mld_hip.metrics.HipTM2TMetrics / HipMMMetrics; at the end of this file).
 
 ``HipT2MEvaluator`` -- the pretrained T2M evaluator nets of a checkpoint (``t2m_moveencoder`` / ``t2m_motionencoder`` / ``t2m_textencoder``:
 mld/models/architectures/t2m_motionenc.py, t2m_textenc.py; instantiated at mld/models/modeltype/mld.py:110-140) as one drop-in module whose arithmetic
@@ -226,3 +227,77 @@ class HipStgcnRecognizer(HipModule):
         """STGCN.forward: {'output': motion, 'features': ..., 'yhat': ...}"""
         yhat, feat = self.recognize(motion)
         return {"output": motion, "features": feat, "yhat": yhat}
+
+
+class HipMetricOps(HipModule):
+    """The device-shaped parts of the text-to-motion metrics (``mldhip_t2m_match`` / ``mldhip_act_stats`` / ``mldhip_pair_dist``; include/mldhip.h has
+    the math) on float32 embeddings that stay on the device.  A module WITHOUT weights: nothing is uploaded and nothing is finalized.
+
+    Inside an ``MLD`` (cfg.model.metric_ops.target = mld_hip.evaluators.HipMetricOps) it shares the model's handle; stand-alone it gets a small handle of
+    its own on the device of the first tensor it is given.  ``metrics_max_rows`` (0: the engine's default, 8192) is the capacity of a call: inputs beyond
+    it raise ``ValueError`` -- there is no silent slicing, a covariance cannot be sliced."""
+    DEFAULT_ROWS = 8192
+
+    def __init__(self, metrics_max_rows: int = 0, **_):
+        super().__init__()
+        self._set_arch("text", t2m_metrics=1, **({"metrics_max_rows": int(metrics_max_rows)} if metrics_max_rows else {}))
+
+    def engine_of(self, t: torch.Tensor):
+        """the handle a call on tensor ``t`` runs on: the injected one, the model's (inside an ``MLD``), or this module's own small one on ``t``'s device"""
+        if self._engine_key is not None:
+            eng = _engine.get_engine(self._engine_key)
+        else:
+            own = {} if self._shared_arch else dict(num_layers=3, max_batch=1, max_frames=16)      # stand-alone: a small handle (the diffusion model is never loaded)
+            eng = _engine.get_engine(t.device, self._variant, want={**self._shared_arch, **self._arch}, **own)
+        _engine.check_arch(eng, type(self).__name__, **self._arch)
+        return eng
+
+    @staticmethod
+    def capacity(eng) -> int:
+        return int(eng.cfg.metrics_max_rows) or HipMetricOps.DEFAULT_ROWS
+
+    def _rows(self, eng, x: torch.Tensor, name: str) -> torch.Tensor:
+        x = self._check(x, name)
+        if x.dim() != 2 or not 1 <= x.shape[1] <= 1024:
+            raise ValueError(f"{name} must be [N, D] with 1 <= D <= 1024, got {tuple(x.shape)}")
+        if x.shape[0] > self.capacity(eng):
+            raise ValueError(f"{name}: {x.shape[0]} rows exceed the engine's metrics_max_rows={self.capacity(eng)} (mldhip_config.metrics_max_rows)")
+        return x
+
+    @torch.no_grad()
+    def match(self, text: torch.Tensor, motion: torch.Tensor, R: int = 32):
+        """text, motion [N, D] -> (rank [G R] int32, diag [G R] float32) with G = N // R: the rank of each row's own motion among its group's and its distance"""
+        eng = self.engine_of(text)
+        t, m = self._rows(eng, text, "text"), self._rows(eng, motion.to(text.device), "motion")
+        if t.shape != m.shape:
+            raise ValueError(f"text {tuple(t.shape)} and motion {tuple(m.shape)} must have one shape")
+        N, D = t.shape
+        n = N // R * R
+        rank = torch.empty(n, dtype=torch.int32, device=t.device)
+        diag = torch.empty(n, dtype=torch.float32, device=t.device)
+        eng.t2m_match(t, m, N, D, R, rank, diag, _engine.current_stream_handle(t))
+        return rank, diag
+
+    @torch.no_grad()
+    def stats(self, x: torch.Tensor):
+        """x [N, D] -> (mean [D], unbiased covariance [D, D]) on the device"""
+        eng = self.engine_of(x)
+        x = self._rows(eng, x, "x")
+        N, D = x.shape
+        if N < 2:
+            raise ValueError("a covariance needs at least two rows")
+        mean = torch.empty(D, dtype=torch.float32, device=x.device)
+        cov = torch.empty(D, D, dtype=torch.float32, device=x.device)
+        eng.act_stats(x, N, D, mean, cov, _engine.current_stream_handle(x))
+        return mean, cov
+
+    @torch.no_grad()
+    def pair_dist(self, x: torch.Tensor, a: Sequence[int], b: Sequence[int]):
+        """x [N, D], host index lists a, b [P] -> ||x[a[p]] - x[b[p]]|| [P] on the device"""
+        eng = self.engine_of(x)
+        x = self._rows(eng, x, "x")
+        if len(a) > self.capacity(eng):
+            raise ValueError(f"{len(a)} pairs exceed the engine's metrics_max_rows={self.capacity(eng)} (mldhip_config.metrics_max_rows)")
+        out = torch.empty(len(a), dtype=torch.float32, device=x.device)
+        eng.pair_dist(x, x.shape[0], x.shape[1], a, b, out, _engine.current_stream_handle(x))
+        return out

@@ -11,7 +11,11 @@ Random draws follow the reference exactly, so under the same seeds the numbers a
   * ``compute`` consumes torch.randperm and np.random in the reference's order (the ground-truth diversity / multimodality with the defaults 200 / 20).
 
 ``HipUESTCMetrics`` (at the end of this file) is the same for the reference's UESTCMetrics (mld/models/metrics/stgcn.py; METRIC.TYPE ['UESTCMetrics']) on the
-recognition ST-GCN (``HipStgcnRecognizer``; ``mldhip_uestc_recognize``): the net draws nothing, so ``update`` is one engine call on cat([rec, gt])."""
+recognition ST-GCN (``HipStgcnRecognizer``; ``mldhip_uestc_recognize``): the net draws nothing, so ``update`` is one engine call on cat([rec, gt]).
+
+``HipTM2TMetrics`` / ``HipMMMetrics`` (behind it) are the text side: drop-ins for TM2TMetrics / MMMetrics (mld/models/metrics/tm2t.py, mm.py) on the embeddings of
+``MLD.t2m_eval``, with the grouped retrieval, the activation statistics and the pair distances in libmldhip (``HipMetricOps``; ``mldhip_t2m_match`` /
+``mldhip_act_stats`` / ``mldhip_pair_dist``)."""
 from __future__ import annotations
 
 from typing import List, Optional
@@ -21,7 +25,7 @@ import scipy.linalg
 import torch
 from torch import Tensor
 
-from .evaluators import HipActionRecognizer, HipStgcnRecognizer
+from .evaluators import HipActionRecognizer, HipMetricOps, HipStgcnRecognizer
 
 
 def calculate_activation_statistics(activations: Tensor):
@@ -181,3 +185,141 @@ class HipUESTCMetrics(HipHUMANACTMetrics):
         self.label_embeddings.append(labels)
         self.recmotion_embeddings.append(feat[:B].squeeze())
         self.gtmotion_embeddings.append(feat[B:].squeeze())
+
+
+class HipTM2TMetrics:
+    """A drop-in for the reference's TM2TMetrics (mld/models/metrics/tm2t.py; METRIC.TYPE ['TM2TMetrics'] of every text config): ``update(text_embeddings,
+    recmotion_embeddings, gtmotion_embeddings, lengths)`` / ``compute(sanity_flag)``, the state names and the 11 metric keys (at ``top_k`` 3), on embeddings
+    that stay on the device: the grouped retrieval, the activation statistics and the pair distances run in libmldhip (``HipMetricOps``; include/mldhip.h has
+    the math).  A plain class (torchmetrics is not a dependency): no reduction across ranks.
+
+    ``compute`` consumes random draws in the reference's order, so under the same seeds the numbers are the reference's: torch.randperm(count_seq) on the CPU
+    generator (the three sets are gathered by it on the device); then np.random.choice(N, diversity_times, replace=False) twice for the generated set and
+    twice for the ground truth.  The matrix square root of the FID stays on the host (``calculate_frechet_distance`` on the float64 casts of the statistics,
+    ground truth first).  ``Matching_score`` / ``gt_Matching_score`` accumulate until ``reset()``, as the reference's states do."""
+
+    def __init__(self, top_k: int = 3, R_size: int = 32, diversity_times: int = 300, ops=None, **kw):
+        """``ops``: an already built HipMetricOps (e.g. ``MLD.metric_ops``, which shares the model's handle); None builds a stand-alone one.  Other keywords
+        (dist_sync_on_step, ...) are accepted and ignored."""
+        self.name = "matching, fid, and diversity scores"
+        self.top_k = top_k
+        self.R_size = R_size
+        self.diversity_times = diversity_times
+        self.ops = ops if ops is not None else HipMetricOps()
+        self.Matching_metrics = ["Matching_score", "gt_Matching_score"] + [f"R_precision_top_{k}" for k in range(1, top_k + 1)] \
+            + [f"gt_R_precision_top_{k}" for k in range(1, top_k + 1)]
+        self.metrics = self.Matching_metrics + ["FID", "Diversity", "gt_Diversity"]
+        self.reset()
+
+    def reset(self):
+        self.count = torch.tensor(0)
+        self.count_seq = torch.tensor(0)
+        for m in self.metrics:
+            setattr(self, m, torch.tensor(0.))
+        self.text_embeddings: List[Tensor] = []
+        self.recmotion_embeddings: List[Tensor] = []
+        self.gtmotion_embeddings: List[Tensor] = []
+
+    def to(self, device):
+        self.ops.to(device)
+        for name in ("text_embeddings", "recmotion_embeddings", "gtmotion_embeddings"):
+            setattr(self, name, [t.to(device) for t in getattr(self, name)])
+        return self
+
+    def _match(self, texts: Tensor, motions: Tensor):
+        """(sum of the groups' traces, top-k hit counts [top_k]) of one pass of the reference's group loop"""
+        rank, diag = self.ops.match(texts, motions, self.R_size)
+        hits = torch.stack([(rank <= k).sum() for k in range(self.top_k)]).cpu().float()
+        return diag.sum().cpu(), hits
+
+    def _diversity(self, x: Tensor):
+        n = x.shape[0]
+        assert n > self.diversity_times
+        first = np.random.choice(n, self.diversity_times, replace=False)
+        second = np.random.choice(n, self.diversity_times, replace=False)
+        return self.ops.pair_dist(x, first, second).cpu().numpy().mean()
+
+    @torch.no_grad()
+    def compute(self, sanity_flag):
+        count_seq = self.count_seq.item()
+        metrics = {m: getattr(self, m) for m in self.metrics}
+        if sanity_flag:
+            return metrics
+        shuffle_idx = torch.randperm(count_seq)
+        dev = self.text_embeddings[0].device
+        idx = shuffle_idx.to(dev)
+        all_texts = torch.cat(self.text_embeddings, axis=0).float()[idx, :].contiguous()
+        all_gen = torch.cat(self.recmotion_embeddings, axis=0).float()[idx, :].contiguous()
+        all_gt = torch.cat(self.gtmotion_embeddings, axis=0).float()[idx, :].contiguous()
+        assert count_seq > self.R_size
+        R_count = count_seq // self.R_size * self.R_size
+        trace, hits = self._match(all_texts, all_gen)
+        self.Matching_score = self.Matching_score + trace
+        metrics["Matching_score"] = self.Matching_score / R_count
+        for k in range(self.top_k):
+            metrics[f"R_precision_top_{k + 1}"] = hits[k] / R_count
+        trace, hits = self._match(all_texts, all_gt)
+        self.gt_Matching_score = self.gt_Matching_score + trace
+        metrics["gt_Matching_score"] = self.gt_Matching_score / R_count
+        for k in range(self.top_k):
+            metrics[f"gt_R_precision_top_{k + 1}"] = hits[k] / R_count
+        mu, cov = (t.cpu().numpy().astype(np.float64) for t in self.ops.stats(all_gen))
+        gt_mu, gt_cov = (t.cpu().numpy().astype(np.float64) for t in self.ops.stats(all_gt))
+        metrics["FID"] = calculate_frechet_distance(gt_mu, gt_cov, mu, cov)
+        assert count_seq > self.diversity_times
+        metrics["Diversity"] = self._diversity(all_gen)
+        metrics["gt_Diversity"] = self._diversity(all_gt)
+        return {**metrics}
+
+    @torch.no_grad()
+    def update(self, text_embeddings: Tensor, recmotion_embeddings: Tensor, gtmotion_embeddings: Tensor, lengths: List[int]):
+        self.count += sum(lengths)
+        self.count_seq += len(lengths)
+        self.text_embeddings.append(torch.flatten(text_embeddings, start_dim=1).detach())
+        self.recmotion_embeddings.append(torch.flatten(recmotion_embeddings, start_dim=1).detach())
+        self.gtmotion_embeddings.append(torch.flatten(gtmotion_embeddings, start_dim=1).detach())
+
+
+class HipMMMetrics:
+    """A drop-in for the reference's MMMetrics (mld/models/metrics/mm.py): ``update(mm_motion_embeddings [1, reps, D], lengths)`` / ``compute(sanity_flag)``
+    -> {'MultiModality'}.  ``compute`` makes the reference's two np.random.choice(reps, mm_num_times, replace=False) draws and runs ONE ``mldhip_pair_dist``
+    call of n x mm_num_times pairs on the flattened [n reps, D] rows."""
+
+    def __init__(self, mm_num_times: int = 10, ops=None, **kw):
+        self.name = "MultiModality scores"
+        self.mm_num_times = mm_num_times
+        self.ops = ops if ops is not None else HipMetricOps()
+        self.metrics = ["MultiModality"]
+        self.reset()
+
+    def reset(self):
+        self.count = torch.tensor(0)
+        self.count_seq = torch.tensor(0)
+        self.MultiModality = torch.tensor(0.)
+        self.mm_motion_embeddings: List[Tensor] = []
+
+    def to(self, device):
+        self.ops.to(device)
+        self.mm_motion_embeddings = [t.to(device) for t in self.mm_motion_embeddings]
+        return self
+
+    @torch.no_grad()
+    def compute(self, sanity_flag):
+        metrics = {m: getattr(self, m) for m in self.metrics}
+        if sanity_flag:
+            return metrics
+        x = torch.cat(self.mm_motion_embeddings, axis=0).float()
+        assert x.dim() == 3
+        n, reps, D = x.shape
+        assert reps > self.mm_num_times
+        first = np.random.choice(reps, self.mm_num_times, replace=False)
+        second = np.random.choice(reps, self.mm_num_times, replace=False)
+        base = np.arange(n)[:, None] * reps
+        dist = self.ops.pair_dist(x.reshape(n * reps, D).contiguous(), (base + first[None, :]).reshape(-1), (base + second[None, :]).reshape(-1))
+        metrics["MultiModality"] = dist.cpu().numpy().reshape(n, self.mm_num_times).mean()
+        return {**metrics}
+
+    def update(self, mm_motion_embeddings: Tensor, lengths: List[int]):
+        self.count += sum(lengths)
+        self.count_seq += len(lengths)
+        self.mm_motion_embeddings.append(mm_motion_embeddings)

@@ -63,14 +63,18 @@ class MLD(nn.Module):
         # the SMPL body model (mld.py:118-143: Rotation2xyz) is opt-in too: cfg.model.smpl.target = mld_hip.smpl.HipSmpl, on action models
         sm = cfg.model.get("smpl") if hasattr(cfg.model, "get") else None
         self.smpl = instantiate_from_config(sm) if sm and sm.get("target") and self.condition == "action" else None
-        for m in (self.vae, self.denoiser, self.text_encoder, self.t2m_evaluator, self.smpl):
+        # the metric kernels (grouped retrieval, activation statistics, pair distances behind mld_hip.metrics.HipTM2TMetrics / HipMMMetrics) are opt-in as well:
+        # cfg.model.metric_ops.target = mld_hip.evaluators.HipMetricOps; the module has no weights and shares this model's handle
+        mo = cfg.model.get("metric_ops") if hasattr(cfg.model, "get") else None
+        self.metric_ops = instantiate_from_config(mo) if mo and mo.get("target") else None
+        for m in (self.vae, self.denoiser, self.text_encoder, self.t2m_evaluator, self.smpl, self.metric_ops):
             if engine_key is not None and m is not None and hasattr(m, "use_engine"):
                 m.use_engine(engine_key)
         # ONE engine for all parts of this model: every part asks the registry for the union of the architecture fields
         # (the fused sample() needs every weight group in one handle); another model with other fields gets its own engine
         shared = {}
         # (the datamodule first: its skeleton -- njoints, the feature width -- then the networks'; a HipMldTextEncoder adds the tower's fields: its weights live in the same handle)
-        for m in (datamodule, self.denoiser, self.vae, self.text_encoder, self.t2m_evaluator, self.smpl):
+        for m in (datamodule, self.denoiser, self.vae, self.text_encoder, self.t2m_evaluator, self.smpl, self.metric_ops):
             shared.update(getattr(m, "_arch", {}) or {})
         if hasattr(self.scheduler, "engine_config"):
             shared.update(self.scheduler.engine_config(cfg.model.scheduler.num_inference_timesteps))
@@ -82,9 +86,11 @@ class MLD(nn.Module):
             self.eta = 0.0
         if self.vae_type != "no":
             shared["eta"] = self.eta
-        for m in (self.denoiser, self.vae, datamodule, self.scheduler, self.text_encoder, self.t2m_evaluator, self.smpl):
+        for m in (self.denoiser, self.vae, datamodule, self.scheduler, self.text_encoder, self.t2m_evaluator, self.smpl, self.metric_ops):
             if m is not None and hasattr(m, "_shared_arch") and engine_key is None:
                 m._shared_arch = shared
+        if self.metric_ops is not None:
+            self.metric_ops._variant = self.variant
         if hasattr(self.text_encoder, "_shared_arch"):
             self.text_encoder._variant = self.variant
         if hasattr(self.scheduler, "_variant"):
