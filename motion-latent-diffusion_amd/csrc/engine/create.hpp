@@ -1,7 +1,6 @@
 // Handle construction and teardown: the cluster-lane lock of a device, config validation, the workspace carve of the two variants,
 // the dynamic-LDS registration list, create_engine / destroy_engine.
-// Part of libmldhip's single translation unit (included by ../mldhip.hip, in this order: state, params, dispatch,
-// path_loop, streams, path_vae, path_latent, path_novae, path_clip, path_eval, path_smpl, path_a2m, path_uestc, path_metrics, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace).
+// Part of libmldhip's single translation unit; include order: see mldhip.hip.  Internal linkage throughout (anonymous namespace).
 #pragma once
 #if !defined(MLDHIP_SIM)
 #include <fcntl.h>
@@ -80,7 +79,18 @@ bool cluster_lane_owned(int device) {
 #endif
 }
 
-// What is wrong with a (full-size) config, or nullptr: the combinations the library is built for (include/mldhip.h "mldhip_config")
+// "0 = default" capacities of the optional modules (include/mldhip.h "mldhip_config"): resolved before config_error reads them; the handle stores the resolved values
+void resolve_defaults(mldhip_config& c) {
+  if (c.clip_layers > 0 && c.clip_max_prompts == 0) c.clip_max_prompts = 2 * c.max_batch;
+  if (c.t2m_eval && c.t2m_max_motions == 0) c.t2m_max_motions = 2 * c.max_batch;
+  if (c.t2m_eval && c.t2m_max_words == 0) c.t2m_max_words = 32;
+  if (c.a2m_rec && c.a2m_max_motions == 0) c.a2m_max_motions = 4 * c.max_batch;
+  if (c.uestc_rec && c.uestc_max_motions == 0) c.uestc_max_motions = 2 * c.max_batch;
+  if (c.uestc_rec && c.uestc_classes == 0) c.uestc_classes = 40;
+  if (c.t2m_metrics && c.metrics_max_rows == 0) c.metrics_max_rows = 8192;
+}
+
+// What is wrong with a (full-size, resolved) config, or nullptr: the combinations the library is built for (include/mldhip.h "mldhip_config")
 const char* config_error(const mldhip_config* cfg) {
   if (!(cfg->eta >= 0.0f && cfg->eta <= 1.0f)) return "eta must be in [0, 1] (DDIMScheduler.step; NaN refused)";
   if (cfg->eta != 0.0f && cfg->scheduler_type != MLDHIP_SCHED_DDIM) return "eta != 0 needs the DDIM scheduler (DDPMScheduler.step has no eta)";

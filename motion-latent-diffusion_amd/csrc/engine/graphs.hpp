@@ -1,7 +1,6 @@
 // Captured graphs: the one capture helper, the per-context cache of sample() graphs, the step-graph cache of the diffusion-only
 // variant, and the one place that destroys a context's graphs.  Every hipGraphExecDestroy of the library is in this file.
-// Part of libmldhip's single translation unit (included by ../mldhip.hip, in this order: state, params, dispatch,
-// path_loop, streams, path_vae, path_latent, path_novae, path_clip, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace).
+// Part of libmldhip's single translation unit; include order: see mldhip.hip.  Internal linkage throughout (anonymous namespace).
 #pragma once
 
 namespace {

@@ -1,11 +1,9 @@
 // Weight contract (SURVEY.md App. B key names), layer binding, scheduler tables, workspace-context plumbing.
-// Part of libmldhip's single translation unit (included by ../mldhip.hip, in this order: state, params, dispatch,
-// path_loop, streams, path_vae, path_latent, path_novae, path_clip, path_eval, path_smpl, path_a2m, path_uestc, path_metrics, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace) except the handle type itself.
+// Part of libmldhip's single translation unit; include order: see mldhip.hip.  Internal linkage throughout (anonymous namespace) except the handle type itself.
 #pragma once
 #include <mutex>
 
 namespace {
-
 
 using E = mldhip_engine;
 
@@ -132,6 +130,30 @@ std::vector<std::string> block_names(int num_block) {
   return v;
 }
 
+// Key -> weight group: the first rule that matches wins, a key no rule matches belongs to the dataset statistics.  Order matters in two places only:
+// "t2m_textencoder." stands before "t2m_", and the four encoder prefixes before "vae.".  mldhip_load_tensor reads the same table (ignorable_key).
+struct GroupRule { const char* pat; bool exact; WeightGroup group; };      // exact: the whole key, else a prefix
+constexpr GroupRule kGroupRules[] = {
+    {"uestc_rec.", false, kGroupUestc}, {"a2m_rec.", false, kGroupA2m}, {"smpl.", false, kGroupSmpl},
+    {"t2m_textencoder.", false, kGroupEvalText},
+    {"t2m_", false, kGroupEvalMotion}, {"mean_eval", true, kGroupEvalMotion}, {"std_eval", true, kGroupEvalMotion},
+    {"denoiser.", false, kGroupDenoiser},
+    {"vae.encoder.", false, kGroupVaeEncoder}, {"vae.skel_embedding.", false, kGroupVaeEncoder}, {"vae.global_motion_token", false, kGroupVaeEncoder}, {"vae.query_pos_encoder.", false, kGroupVaeEncoder},
+    {"vae.", false, kGroupVaeDecoder},
+    {"text_encoder.", false, kGroupClip},
+};
+bool has_prefix(const char* key, const char* p) { return std::strncmp(key, p, std::strlen(p)) == 0; }
+const GroupRule* group_rule(const char* key) {
+  for (const GroupRule& r : kGroupRules)
+    if (r.exact ? std::strcmp(key, r.pat) == 0 : has_prefix(key, r.pat)) return &r;
+  return nullptr;
+}
+// A key the handle did not declare is skipped, not refused, under an optional module's prefix (the module is off, or has no use for that tensor) and for two tensors the engine never reads
+bool ignorable_key(const char* key) {
+  const GroupRule* r = group_rule(key);
+  return (r && !r->exact && optional_group(r->group)) || has_prefix(key, "denoiser.mem_pos.") || has_prefix(key, "vae.dist_layer.");
+}
+
 size_t add_param(E* e, const std::string& key, std::vector<int64_t> shape) {
   Param p;
   p.key = key;
@@ -139,10 +161,8 @@ size_t add_param(E* e, const std::string& key, std::vector<int64_t> shape) {
   p.numel = 1;
   for (auto s : shape) p.numel *= size_t(s);
   p.offset = e->arena_floats;
-  const bool enc = key.rfind("vae.encoder.", 0) == 0 || key.rfind("vae.skel_embedding.", 0) == 0 ||
-                   key.rfind("vae.global_motion_token", 0) == 0 || key.rfind("vae.query_pos_encoder.", 0) == 0;
-  const bool ev_text = key.rfind("t2m_textencoder.", 0) == 0, ev_motion = !ev_text && (key.rfind("t2m_", 0) == 0 || key == "mean_eval" || key == "std_eval");
-  p.group = key.rfind("uestc_rec.", 0) == 0 ? 9 : key.rfind("a2m_rec.", 0) == 0 ? 8 : key.rfind("smpl.", 0) == 0 ? 7 : ev_text ? 6 : ev_motion ? 5 : key.rfind("denoiser.", 0) == 0 ? 0 : enc ? 3 : key.rfind("vae.", 0) == 0 ? 1 : key.rfind("text_encoder.", 0) == 0 ? 4 : 2;
+  const GroupRule* rule = group_rule(key.c_str());
+  p.group = rule ? rule->group : kGroupStats;
   e->arena_floats += align_up(p.numel);
   e->index[key] = int(e->params.size());
   e->params.push_back(p);

@@ -4,7 +4,7 @@
 //
 // A call uploads the lengths and issues ONE a2m_gru_kernel launch: a workgroup per 16-motion tile runs both layers over the tile's steps and the head.
 // No tables are derived at finalize: the kernel reads the a2m_rec.* tensors of the arena as they are.
-// Issued eagerly.  Exact fp32 in every precision mode.  Part of libmldhip's single translation unit (after path_smpl.hpp).
+// Issued eagerly.  Exact fp32 in every precision mode.  Part of libmldhip's single translation unit; include order: see mldhip.hip.
 #pragma once
 
 namespace {
@@ -13,7 +13,7 @@ int a2m_recognize_impl(E* e, const float* joints_dev, const int32_t* lens_host, 
                        hipStream_t stream) {
   const auto& cfg = e->cfg;
   if (!cfg.a2m_rec) return e->fail(MLDHIP_ESTATE, "mldhip_a2m_recognize: the handle was created without the recognition GRU (mldhip_config.a2m_rec = 0)");
-  if (!e->finalized || !e->group_ready[8]) return e->fail(MLDHIP_ESTATE, "mldhip_a2m_recognize before finalize / the a2m_rec.* tensors not loaded");
+  if (!e->finalized || !e->group_ready[kGroupA2m]) return e->fail(MLDHIP_ESTATE, "mldhip_a2m_recognize before finalize / the a2m_rec.* tensors not loaded");
   if (!joints_dev || !lens_host) return e->fail(MLDHIP_EINVAL, "null pointer");
   if (!logits_dev && !act_dev) return e->fail(MLDHIP_EINVAL, "logits_out_dev and act_out_dev are both NULL: nothing to compute");
   if (B < 1 || B > cfg.a2m_max_motions) return e->fail(MLDHIP_EINVAL, "B=%d must be in 1..a2m_max_motions=%d", B, cfg.a2m_max_motions);

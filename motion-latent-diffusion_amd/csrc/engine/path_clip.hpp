@@ -4,7 +4,7 @@
 //      contributes n_p = eos_pos[p] + 1 rows, all prompts packed into one [sum n_p][D] activation;
 //   2. duplicates -- identical id rows (the B copies of "" of a classifier-free-guidance batch) are computed once and stored to every copy;
 //   3. the pooled output needs final_layer_norm and the projection at the EOS rows only.
-// Issued eagerly (the row total changes per call: no hipGraph).  Part of libmldhip's single translation unit (after dispatch.hpp).
+// Issued eagerly (the row total changes per call: no hipGraph).  Part of libmldhip's single translation unit; include order: see mldhip.hip.
 #pragma once
 
 namespace {
@@ -30,7 +30,7 @@ ClipLayerP bind_clip_layer(E* e, int i) {
 int text_encode_impl(E* e, const int32_t* ids_host, const int32_t* eos_host, int NP, float* out_dev, hipStream_t stream, bool count = true) {
   const auto& cfg = e->cfg;
   if (cfg.clip_layers <= 0) return e->fail(MLDHIP_ESTATE, "mldhip_text_encode: the handle was created without a text tower (mldhip_config.clip_layers = 0)");
-  if (!e->finalized || !e->group_ready[4]) return e->fail(MLDHIP_ESTATE, "mldhip_text_encode before finalize / text_encoder.* tower tensors not loaded");
+  if (!e->finalized || !e->group_ready[kGroupClip]) return e->fail(MLDHIP_ESTATE, "mldhip_text_encode before finalize / text_encoder.* tower tensors not loaded");
   if (!ids_host || !eos_host || !out_dev) return e->fail(MLDHIP_EINVAL, "null pointer");
   if (NP < 1 || NP > cfg.clip_max_prompts) return e->fail(MLDHIP_EINVAL, "P=%d must be in 1..clip_max_prompts=%d", NP, cfg.clip_max_prompts);
   const int ctx = cfg.clip_ctx, W = cfg.text_dim, H = cfg.clip_heads;
@@ -69,7 +69,7 @@ int text_encode_impl(E* e, const int32_t* ids_host, const int32_t* eos_host, int
   const int32_t *d_tok = dtab, *d_pos = d_tok + R, *d_off = d_pos + R, *d_cnt = d_off + U, *d_eos = d_cnt + U, *d_dup = d_eos + U;
 
   Ctx c{e, stream};
-  const bool x3 = cfg.precision == MLDHIP_PREC_F16X3 && e->arena_x3 && e->text_split_ok;      // text_split_ok: finalize's range probe
+  const bool x3 = cfg.precision == MLDHIP_PREC_F16X3 && e->arena_x3 && e->probe[kProbeText].ok;      // the verdict of finalize's range probe
   const unsigned ew = (unsigned)std::min<long long>(2048, ((long long)R * W / 4 + 255) / 256);
   MLD_LAUNCH(clip_embed_kernel, dim3(ew), dim3(256), 0, stream, P(e, std::string(kClipText) + "embeddings.token_embedding.weight"),
              P(e, std::string(kClipText) + "embeddings.position_embedding.weight"), d_tok, d_pos, e->cX, R, W);

@@ -13,7 +13,7 @@
 //   recurrence  one gru_step_kernel launch per step (max over the chunk of len / 4), state double buffered in vH0 / vH1 as [B][h_fwd | h_bwd] -- which IS the cat() the head reads;
 //   head        Linear(2048 -> 1024), LayerNorm + LeakyReLU, Linear(1024 -> 512) straight into the caller's rows.
 // Text tower: staging (word + Linear(15 -> 300)(pos) into K = 384 rows), input_emb, the GRU at H = 512 over L rows per caption, the same head at half the widths.
-// Issued eagerly.  Part of libmldhip's single translation unit (after path_clip.hpp).
+// Issued eagerly.  Part of libmldhip's single translation unit; include order: see mldhip.hip.
 #pragma once
 
 namespace {
@@ -23,7 +23,7 @@ int eval_tp(int T) { return (T + 4 + 3) / 4 * 4; }      // staging rows per moti
 // finalize: the tables the towers derive from their weights (tap-major convolution weights, the padded text input weight, the folded GRU input biases)
 int build_eval_tables(Ctx& c) {
   E* e = c.e;
-  if (!e->cfg.t2m_eval || (!e->group_ready[5] && !e->group_ready[6])) return MLDHIP_OK;
+  if (!e->cfg.t2m_eval || (!e->group_ready[kGroupEvalMotion] && !e->group_ready[kGroupEvalText])) return MLDHIP_OK;
   const size_t n1 = (size_t)kEvalMove * 4 * kEvalConvC, n2 = (size_t)kEvalMove * 4 * kEvalMove, n3 = (size_t)kEvalTextH * kEvalTextK, n4 = 6 * kEvalMotionH, n5 = 6 * kEvalTextH;
   if (!e->eval_tabs && hipMalloc((void**)&e->eval_tabs, (n1 + n2 + n3 + n4 + n5) * sizeof(float)) != hipSuccess) return e->fail(MLDHIP_EHIP, "hipMalloc(evaluator tables)");
   e->ev_conv1_w = e->eval_tabs; e->ev_conv2_w = e->ev_conv1_w + n1; e->ev_text_in_w = e->ev_conv2_w + n2; e->ev_mbias = e->ev_text_in_w + n3; e->ev_tbias = e->ev_mbias + n4;
@@ -32,13 +32,13 @@ int build_eval_tables(Ctx& c) {
                P(e, p + ".gru.bias_ih_l0_reverse"), P(e, p + ".gru.bias_hh_l0_reverse"), H);
     check_launch(c, "gru_input_bias");
   };
-  if (e->group_ready[5]) {
+  if (e->group_ready[kGroupEvalMotion]) {
     MLD_LAUNCH(conv_weight_relay_kernel, dim3(1024), dim3(256), 0, c.stream, P(e, "t2m_moveencoder.main.0.weight"), e->ev_conv1_w, kEvalMove, e->cfg.nfeats - 4, kEvalConvC);
     MLD_LAUNCH(conv_weight_relay_kernel, dim3(1024), dim3(256), 0, c.stream, P(e, "t2m_moveencoder.main.3.weight"), e->ev_conv2_w, kEvalMove, kEvalMove, kEvalMove);
     check_launch(c, "conv_weight_relay");
     bias(e->ev_mbias, "t2m_motionencoder", kEvalMotionH);
   }
-  if (e->group_ready[6]) {
+  if (e->group_ready[kGroupEvalText]) {
     MLD_LAUNCH(pad_cols_kernel, dim3((kEvalTextH * kEvalTextK + 255) / 256), dim3(256), 0, c.stream, P(e, "t2m_textencoder.input_emb.weight"), e->ev_text_in_w, kEvalTextH, kEvalWord, kEvalTextK);
     check_launch(c, "pad_cols");
     bias(e->ev_tbias, "t2m_textencoder", kEvalTextH);
@@ -46,7 +46,7 @@ int build_eval_tables(Ctx& c) {
   return c.rc;
 }
 
-bool eval_x3(const E* e) { return e->cfg.precision == MLDHIP_PREC_F16X3 && e->arena_x3 && e->eval_split_ok; }      // eval_split_ok: finalize's range probe
+bool eval_x3(const E* e) { return e->cfg.precision == MLDHIP_PREC_F16X3 && e->arena_x3 && e->probe[kProbeEval].ok; }      // the verdict of finalize's range probe
 
 // the bidirectional recurrence of one chunk: `steps` launches in stream order; returns the buffer that holds the final state [B][2H]
 template <int H>
@@ -89,10 +89,10 @@ int eval_count_nonfinite(Ctx& c, const float* out, int B) {
 int t2m_motion_embed_impl(E* e, const float* feats_dev, const int32_t* lens_host, int B, int T, int renorm, float* out_dev, hipStream_t stream, bool count = true) {
   const auto& cfg = e->cfg;
   if (!cfg.t2m_eval) return e->fail(MLDHIP_ESTATE, "mldhip_t2m_motion_embed: the handle was created without the evaluator towers (mldhip_config.t2m_eval = 0)");
-  if (!e->finalized || !e->group_ready[5]) return e->fail(MLDHIP_ESTATE, "mldhip_t2m_motion_embed before finalize / t2m_moveencoder.*, t2m_motionencoder.*, mean_eval, std_eval not loaded");
+  if (!e->finalized || !e->group_ready[kGroupEvalMotion]) return e->fail(MLDHIP_ESTATE, "mldhip_t2m_motion_embed before finalize / t2m_moveencoder.*, t2m_motionencoder.*, mean_eval, std_eval not loaded");
   if (!feats_dev || !lens_host || !out_dev) return e->fail(MLDHIP_EINVAL, "null pointer");
   if (renorm != 0 && renorm != 1) return e->fail(MLDHIP_EINVAL, "renorm=%d must be 0 or 1", renorm);
-  if (renorm && !e->group_ready[2]) return e->fail(MLDHIP_ESTATE, "mldhip_t2m_motion_embed with renorm = 1 needs mean / std");
+  if (renorm && !e->group_ready[kGroupStats]) return e->fail(MLDHIP_ESTATE, "mldhip_t2m_motion_embed with renorm = 1 needs mean / std");
   if (B < 1 || B > cfg.t2m_max_motions) return e->fail(MLDHIP_EINVAL, "B=%d must be in 1..t2m_max_motions=%d", B, cfg.t2m_max_motions);
   if (T < 1 || T > cfg.max_frames) return e->fail(MLDHIP_EINVAL, "T=%d must be in 1..max_frames=%d", T, cfg.max_frames);
   for (int b = 0; b < B; ++b)
@@ -140,7 +140,7 @@ int t2m_motion_embed_impl(E* e, const float* feats_dev, const int32_t* lens_host
 int t2m_text_embed_impl(E* e, const float* word_dev, const float* pos_dev, const int32_t* lens_host, int B, int L, float* out_dev, hipStream_t stream, bool count = true) {
   const auto& cfg = e->cfg;
   if (!cfg.t2m_eval) return e->fail(MLDHIP_ESTATE, "mldhip_t2m_text_embed: the handle was created without the evaluator towers (mldhip_config.t2m_eval = 0)");
-  if (!e->finalized || !e->group_ready[6]) return e->fail(MLDHIP_ESTATE, "mldhip_t2m_text_embed before finalize / t2m_textencoder.* not loaded");
+  if (!e->finalized || !e->group_ready[kGroupEvalText]) return e->fail(MLDHIP_ESTATE, "mldhip_t2m_text_embed before finalize / t2m_textencoder.* not loaded");
   if (!word_dev || !pos_dev || !lens_host || !out_dev) return e->fail(MLDHIP_EINVAL, "null pointer");
   if (B < 1 || B > cfg.t2m_max_motions) return e->fail(MLDHIP_EINVAL, "B=%d must be in 1..t2m_max_motions=%d", B, cfg.t2m_max_motions);
   if (L < 1 || L > cfg.t2m_max_words) return e->fail(MLDHIP_EINVAL, "L=%d must be in 1..t2m_max_words=%d", L, cfg.t2m_max_words);

@@ -1,7 +1,5 @@
 // Latent-diffusion paths (configs 1-3, 5): what a sample call is made of -- condition rows, the reverse loop (path_loop.hpp), decode + joints (path_vae.hpp).
-// Part of libmldhip's single translation unit (included by ../mldhip.hip, in this order: state, params, dispatch,
-// path_loop, streams, path_vae, path_latent, path_novae, path_clip, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace)
-// except the handle type itself.
+// Part of libmldhip's single translation unit; include order: see mldhip.hip.  Internal linkage throughout (anonymous namespace) except the handle type itself.
 #pragma once
 
 namespace {

@@ -1,8 +1,6 @@
 // The reverse loop of the latent models (configs 1-3, 5): the per-launch denoiser chain on its two kernel families, which family or loop kernel a call
 // takes, and the launches of the persistent loop and the cluster loop.
-// Part of libmldhip's single translation unit (included by ../mldhip.hip, in this order: state, params, dispatch,
-// path_loop, streams, path_vae, path_latent, path_novae, path_clip, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace)
-// except the handle type itself.
+// Part of libmldhip's single translation unit; include order: see mldhip.hip.  Internal linkage throughout (anonymous namespace) except the handle type itself.
 #pragma once
 
 namespace {

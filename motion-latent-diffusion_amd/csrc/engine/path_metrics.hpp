@@ -4,7 +4,7 @@
 //
 // No weights and nothing derived at finalize: the calls work on any handle created with t2m_metrics = 1, finalized or not.  The only workspace is the
 // index table of mldhip_pair_dist (2 x metrics_max_rows words), uploaded with the call like the length tables of the other entry points.
-// Issued eagerly.  Exact fp32 in every precision mode.  Part of libmldhip's single translation unit (after path_uestc.hpp).
+// Issued eagerly.  Exact fp32 in every precision mode.  Part of libmldhip's single translation unit; include order: see mldhip.hip.
 #pragma once
 
 namespace {

@@ -7,7 +7,7 @@
 // a call     uploads the lengths, then per chunk of up to kSmplChunk frames: smpl_chain_kernel (joints, and the pose features / skinning matrices / per-frame
 //            state of the chunk into the workspace) and, when vertices are asked for, smpl_verts_kernel.  A frame's numbers do not depend on the chunk or tile
 //            it falls into: every product is a row of a matrix instruction whose other rows are other frames.
-// Issued eagerly.  Exact fp32 in every precision mode.  Part of libmldhip's single translation unit (after path_eval.hpp).
+// Issued eagerly.  Exact fp32 in every precision mode.  Part of libmldhip's single translation unit; include order: see mldhip.hip.
 #pragma once
 
 namespace {
@@ -18,7 +18,7 @@ int smpl_chunk_frames(const E* e) { return (int)std::min<long long>(kSmplChunk, 
 
 int build_smpl_tables(Ctx& c) {
   E* e = c.e;
-  if (e->cfg.smpl_verts <= 0 || !e->group_ready[7]) return MLDHIP_OK;
+  if (e->cfg.smpl_verts <= 0 || !e->group_ready[kGroupSmpl]) return MLDHIP_OK;
   const int V = e->cfg.smpl_verts, nblk = smpl_blocks(e);
   std::vector<float> par(kSmplJoints), vt((size_t)V * 3), jreg((size_t)kSmplJoints * V);
   HIP_TRY(e, hipMemcpy(par.data(), P(e, "smpl.parents"), par.size() * sizeof(float), hipMemcpyDeviceToHost));
@@ -54,7 +54,7 @@ int build_smpl_tables(Ctx& c) {
 int smpl_forward_impl(E* e, const float* feats_dev, const int32_t* lens_host, int B, int T, int flags, float* joints_dev, float* verts_dev, hipStream_t stream) {
   const auto& cfg = e->cfg;
   if (cfg.smpl_verts <= 0) return e->fail(MLDHIP_ESTATE, "mldhip_smpl_forward: the handle was created without the body model (mldhip_config.smpl_verts = 0)");
-  if (!e->finalized || !e->group_ready[7]) return e->fail(MLDHIP_ESTATE, "mldhip_smpl_forward before finalize / smpl.v_template, smpl.posedirs, smpl.J_regressor, smpl.lbs_weights, smpl.parents not loaded");
+  if (!e->finalized || !e->group_ready[kGroupSmpl]) return e->fail(MLDHIP_ESTATE, "mldhip_smpl_forward before finalize / smpl.v_template, smpl.posedirs, smpl.J_regressor, smpl.lbs_weights, smpl.parents not loaded");
   if (!feats_dev || !lens_host) return e->fail(MLDHIP_EINVAL, "null pointer");
   if (!joints_dev && !verts_dev) return e->fail(MLDHIP_EINVAL, "joints_out_dev and verts_out_dev are both NULL: nothing to compute");
   if (flags & ~(MLDHIP_SMPL_TRANS_JOINTS | MLDHIP_SMPL_TRANS_VERTS)) return e->fail(MLDHIP_EINVAL, "flags=%d: unknown bits (MLDHIP_SMPL_TRANS_JOINTS | MLDHIP_SMPL_TRANS_VERTS)", flags);

@@ -11,7 +11,7 @@
 // A CALL runs chunks of as many motions as the workspace holds at the call's T.  Per chunk: input stage (gather, data_bn, block 0's mix), then per block
 //   [mix] -> graph GEMM (+ bias table, ReLU) into the padded H -> [residual GEMM into R] -> temporal GEMM over overlapping rows of H (+ bias, + residual, ReLU)
 //   into the padded input of the next block;  then the pool + head kernel.  Zero rows of a padded buffer are rewritten only when its geometry changes.
-// Issued eagerly.  Part of libmldhip's single translation unit (after path_a2m.hpp).
+// Issued eagerly.  Part of libmldhip's single translation unit; include order: see mldhip.hip.
 #pragma once
 
 namespace {
@@ -29,11 +29,11 @@ constexpr int kUestcChunk = 64;      // motions the workspace holds at T = max_f
 constexpr size_t kUestcWsCap = (size_t)128 << 20;      // ... but no more than 512 MB of workspace (33 motions at 196 frames), and at least one motion
 constexpr size_t kUestcSlack = 2 * kStgFeat;
 
-bool uestc_x3(const E* e) { return e->cfg.precision == MLDHIP_PREC_F16X3 && e->uestc_tabs_x3 && e->uestc_split_ok; }      // uestc_split_ok: finalize's range probe
+bool uestc_x3(const E* e) { return e->cfg.precision == MLDHIP_PREC_F16X3 && e->uestc_tabs_x3 && e->probe[kProbeUestc].ok; }      // the verdict of finalize's range probe
 
 int build_uestc_tables(Ctx& c) {
   E* e = c.e;
-  if (!e->cfg.uestc_rec || !e->group_ready[9]) return MLDHIP_OK;
+  if (!e->cfg.uestc_rec || !e->group_ready[kGroupUestc]) return MLDHIP_OK;
   const std::string p = "uestc_rec.";
   auto host = [&](const std::string& key, std::vector<double>& out) -> int {
     const Param& q = e->params[e->index.at(p + key)];
@@ -148,7 +148,7 @@ void uestc_pads(Ctx& c, UestcPadded& b, int G, int T, int C) {
 int uestc_recognize_impl(E* e, const float* x_dev, const int64_t* strides, int B, int T, float* logits_dev, float* feat_dev, hipStream_t stream, bool count = true) {
   const auto& cfg = e->cfg;
   if (!cfg.uestc_rec) return e->fail(MLDHIP_ESTATE, "mldhip_uestc_recognize: the handle was created without the recognition ST-GCN (mldhip_config.uestc_rec = 0)");
-  if (!e->finalized || !e->group_ready[9]) return e->fail(MLDHIP_ESTATE, "mldhip_uestc_recognize before finalize / the uestc_rec.* tensors not loaded");
+  if (!e->finalized || !e->group_ready[kGroupUestc]) return e->fail(MLDHIP_ESTATE, "mldhip_uestc_recognize before finalize / the uestc_rec.* tensors not loaded");
   if (!x_dev || !strides) return e->fail(MLDHIP_EINVAL, "null pointer");
   if (!logits_dev && !feat_dev) return e->fail(MLDHIP_EINVAL, "logits_out_dev and feat_out_dev are both NULL: nothing to compute");
   if (B < 1 || B > cfg.uestc_max_motions) return e->fail(MLDHIP_EINVAL, "B=%d must be in 1..uestc_max_motions=%d", B, cfg.uestc_max_motions);

@@ -1,7 +1,5 @@
 // The VAE of the latent models: MldVae / ActorVae decode and encode on the decoder's kernels, feats2joints.
-// Part of libmldhip's single translation unit (included by ../mldhip.hip, in this order: state, params, dispatch,
-// path_loop, streams, path_vae, path_latent, path_novae, path_clip, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace)
-// except the handle type itself.
+// Part of libmldhip's single translation unit; include order: see mldhip.hip.  Internal linkage throughout (anonymous namespace) except the handle type itself.
 #pragma once
 
 namespace {
@@ -113,10 +111,10 @@ void ffn_block(Ctx& c, const float* x, float* y, int M, const float* w1, const f
   gemm_ln(c, f2);
 }
 
-// The decoder's self-attention block on half Q | K | V (kernels/dec_half.hpp; option "dec_half", verdict of finalize's probe in dec_half_ok): split mode,
+// The decoder's self-attention block on half Q | K | V (kernels/dec_half.hpp; option "dec_half", verdict of finalize's probe in probe[kProbeDecodeHalf]): split mode,
 // row-strip kernels on, D = 256 as 4 heads of 64, at most 16 query tiles per (sample, head)
 bool dec_half_on(const E* e, int T) {
-  return e->dec_half && (e->dec_half_ok || e->dec_half == 2) && staged_prec(e) == PREC_F16X3 && e->strip_gemm && !e->trace_on && e->cfg.latent_dim == 256 &&
+  return e->dec_half && (e->probe[kProbeDecodeHalf].ok || e->dec_half == 2) && staged_prec(e) == PREC_F16X3 && e->strip_gemm && !e->trace_on && e->cfg.latent_dim == 256 &&
          e->cfg.num_heads == 4 && T <= 256;
 }
 

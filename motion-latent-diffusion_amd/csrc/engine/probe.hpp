@@ -1,8 +1,8 @@
 // Range probe of the F16X3 mode (include/mldhip.h "Range contract"): the split-f16 kernels against the exact-fp32 ones of the SAME
-// handle on one seeded probe batch; a stage that disagrees (or is not finite) is switched to the fp32 kernels.  Four stages -- the reverse
-// loop, the decoder, the diffusion-only denoiser, the CLIP text tower -- over one seeded generator and the helpers at the top.
-// Part of libmldhip's single translation unit (included by ../mldhip.hip, in this order: state, params, dispatch,
-// path_loop, streams, path_vae, path_latent, path_novae, path_clip, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace).
+// handle on one seeded probe batch; a stage that disagrees (or is not finite) is switched to the fp32 kernels.  Six stages, each run only where the handle has its weights: 1 the
+// reverse loop, 2 the decoder, 3 the diffusion-only denoiser (in place of 1 and 2), 4 the CLIP text tower, 5 the T2M evaluator towers, 6 the UESTC recognition ST-GCN.  They share ONE
+// seeded generator (a draw more or less in one stage moves the inputs of every later one) and the helpers at the top; verdicts go to the handle's probe[] (engine/state.hpp ProbeStage).
+// Part of libmldhip's single translation unit; include order: see mldhip.hip.  Internal linkage throughout (anonymous namespace).
 #pragma once
 
 namespace {
@@ -53,6 +53,20 @@ int probe_down(E* e, hipStream_t stream, const float* dev, size_t n, std::vector
   return MLDHIP_OK;
 }
 
+// One pair of runs of a stage: run(split) with the stage's flag on split arithmetic, then on exact fp32 (the stage's verdict overwrites the flag afterwards); after each
+// run n floats at `dev` come down into ha (split) / hb (fp32).  The first error ends the pair.
+template <class Run>
+int probe_pair(E* e, hipStream_t stream, ProbeStage stage, const float* dev, size_t n, std::vector<float>& ha, std::vector<float>& hb, Run run) {
+  for (int split = 1; split >= 0; --split) {
+    e->probe[stage].ok = split != 0;
+    if (int rc = run(split != 0)) return rc;
+    if (int rc = probe_down(e, stream, dev, n, split ? ha : hb)) return rc;
+  }
+  return MLDHIP_OK;
+}
+
+void probe_verdict(E* e, ProbeStage stage, float err) { e->probe[stage] = {err <= MLDHIP_PROBE_TOL, err}; }
+
 // max difference d over reference magnitude m (over an amplification the stage allows for); inf when anything was not finite, or differs from an all-zero reference
 float probe_ratio(bool finite, float d, float m, float amp = 1.0f) {
   const float inf = std::numeric_limits<float>::infinity();
@@ -87,11 +101,8 @@ int probe_loop_denoiser(LoopProbe& p) {
   std::vector<float> ha, hb;
   for (int which = 0; which < 2; ++which) {
     const int t = e->timesteps[which == 0 ? 0 : n - 1];
-    for (int split = 1; split >= 0; --split) {
-      e->split_loop_ok = split != 0;
-      if (int rc = denoiser_forward_impl(e, p.sample.p, t, is_action(e) ? nullptr : p.text.p, is_action(e) ? p.act.data() : nullptr, 2 * p.Bp, p.out.p, p.stream)) return rc;
-      if (int rc = probe_down(e, p.stream, p.out.p, (size_t)2 * p.Bp * D, split ? ha : hb)) return rc;
-    }
+    auto run = [&](bool) { return denoiser_forward_impl(e, p.sample.p, t, is_action(e) ? nullptr : p.text.p, is_action(e) ? p.act.data() : nullptr, 2 * p.Bp, p.out.p, p.stream); };
+    if (int rc = probe_pair(e, p.stream, kProbeLoop, p.out.p, (size_t)2 * p.Bp * D, ha, hb, run)) return rc;
     p.worst = std::max(p.worst, rel_err(ha, hb));
   }
   return MLDHIP_OK;
@@ -102,7 +113,7 @@ int probe_loop_denoiser(LoopProbe& p) {
 int probe_loop_cluster(LoopProbe& p, Ctx& c, const std::vector<float>& hb, float m, float amp, float guidance) {
   E* e = p.e;
   const int D = e->cfg.latent_dim, n = e->cfg.num_inference_steps, Bp = p.Bp;
-  e->split_loop_ok = true;
+  e->probe[kProbeLoop].ok = true;
   // both forms (advisor r5): 8 column groups per token (24 workgroups per cluster: calls of up to 64 motions -- what a probe batch of 8 picks by itself) and 4 (12 workgroups:
   // calls of 65 .. 256 motions); they differ in how linear1 / linear2 / the skip linear are split over members and waves, i.e. in the order of sums
   Scoped<int> restore_cg(e->cluster_groups, e->cluster_groups);
@@ -140,18 +151,16 @@ int probe_loop_steps(LoopProbe& p) {
   e->phase = 0;
   const float guidance = e->cfg.guidance_scale > 1.0f ? e->cfg.guidance_scale : 1.0f;
   std::vector<float> ha, hb;
-  for (int split = 1; split >= 0; --split) {
-    e->split_loop_ok = split != 0;
-    if (is_action(e)) {
-      HIP_TRY(e, hipMemcpyAsync(e->labels_dev, p.act.data(), p.act.size() * sizeof(int32_t), hipMemcpyHostToDevice, p.stream));
-      action_rows(c, 2 * Bp, Bp, e->TP);
-    } else {
-      text_projection(c, p.text.p, 2 * Bp, e->TP);
-    }
-    launch_fused_loop(c, p.sample.p, Bp, std::min(2, n), guidance);
-    if (c.rc) return c.rc;
-    if (int rc = probe_down(e, p.stream, e->lat, (size_t)Bp * D, split ? ha : hb)) return rc;
-  }
+  if (int rc = probe_pair(e, p.stream, kProbeLoop, e->lat, (size_t)Bp * D, ha, hb, [&](bool) -> int {
+        if (is_action(e)) {
+          HIP_TRY(e, hipMemcpyAsync(e->labels_dev, p.act.data(), p.act.size() * sizeof(int32_t), hipMemcpyHostToDevice, p.stream));
+          action_rows(c, 2 * Bp, Bp, e->TP);
+        } else {
+          text_projection(c, p.text.p, 2 * Bp, e->TP);
+        }
+        launch_fused_loop(c, p.sample.p, Bp, std::min(2, n), guidance);
+        return c.rc;
+      })) return rc;
   // measured against the UPDATE the two steps made (latents - start noise), not against the latents: near t = T a DDIM step moves
   // x by a few per cent, and how much depends on the schedule; the update is (guided eps) x (step coefficients), so this reads
   // like (a) times the guidance amplification (2 g - 1 at worst) -- hence the factor on the tolerance
@@ -195,9 +204,8 @@ int probe_loop(E* e, hipStream_t stream, ProbeRng& rng, const float* user_text, 
   if (int rc = probe_loop_denoiser(p)) return rc;
   if (e->loop_ips > 0 && e->loop_stream_x3)
     if (int rc = probe_loop_steps(p)) return rc;
-  if (user) p.worst = std::max(p.worst, e->probe_err_loop);          // the verdict covers the seeded batch AND the caller's
-  e->probe_err_loop = p.worst;
-  e->split_loop_ok = p.worst <= MLDHIP_PROBE_TOL;
+  if (user) p.worst = std::max(p.worst, e->probe[kProbeLoop].err);          // the verdict covers the seeded batch AND the caller's
+  probe_verdict(e, kProbeLoop, p.worst);
   return MLDHIP_OK;
 }
 
@@ -227,9 +235,10 @@ int probe_decoder(E* e, hipStream_t stream, ProbeRng& rng) {
   };
   const int dh = e->dec_half;
   Scoped<int> restore_dh(e->dec_half, dh);
-  e->split_decode_ok = false;                    // the exact-fp32 decode: the reference of every form below
+  bool& split = e->probe[kProbeDecode].ok;
+  split = false;                                 // the exact-fp32 decode: the reference of every form below
   if (int rc = run(hb)) return rc;
-  e->split_decode_ok = true;
+  split = true;
   float worst = 0.f;
   for (int form = 0; form < 2; ++form) {         // fp32 Q | K | V, split x3 products: key-blocked and whole-K/V attention
     e->dec_half = 0;
@@ -245,17 +254,15 @@ int probe_decoder(E* e, hipStream_t stream, ProbeRng& rng) {
     rng.fill(hz1, 1.0f);
     HIP_TRY(e, hipMemcpy(z.p, hz1.data(), hz1.size() * sizeof(float), hipMemcpyHostToDevice));
     e->dec_half = 0;
-    e->split_decode_ok = false;
+    split = false;
     if (int rc = run(hb)) return rc;
-    e->split_decode_ok = true;
+    split = true;
     e->dec_half = 2;
     if (int rc = run(ha)) return rc;
     half_err = rel_err(ha, hb);
   }
-  e->probe_err_decode = worst;
-  e->split_decode_ok = worst <= MLDHIP_PROBE_TOL;
-  e->probe_err_decode_half = half_err;
-  e->dec_half_ok = !dh || (half_err >= 0.f && half_err <= MLDHIP_PROBE_TOL_HALF);      // (option off: nothing to veto; switching it on later un-finalizes the handle, mldhip_set_option)
+  probe_verdict(e, kProbeDecode, worst);
+  e->probe[kProbeDecodeHalf] = {!dh || (half_err >= 0.f && half_err <= MLDHIP_PROBE_TOL_HALF), half_err};      // (option off: nothing to veto; switching it on later un-finalizes the handle, mldhip_set_option)
   return MLDHIP_OK;
 }
 
@@ -278,15 +285,11 @@ int probe_novae(E* e, hipStream_t stream, ProbeRng& rng) {
   for (int form = 0; form < 2; ++form) {
     e->flash_attn = form == 0 ? 2 : 0;
     e->gemm_pipe = form == 0 ? pipe.saved : 0;
-    for (int split = 1; split >= 0; --split) {
-      e->split_decode_ok = split != 0;
-      if (int rc = denoiser_forward_novae_impl(e, x.p, e->timesteps[0], text.p, lens.data(), R, T, out.p, stream)) return rc;
-      if (int rc = probe_down(e, stream, out.p, (size_t)R * T * NF, split ? ha : hb)) return rc;
-    }
+    auto run = [&](bool) { return denoiser_forward_novae_impl(e, x.p, e->timesteps[0], text.p, lens.data(), R, T, out.p, stream); };
+    if (int rc = probe_pair(e, stream, kProbeDecode, out.p, (size_t)R * T * NF, ha, hb, run)) return rc;
     worst = std::max(worst, rel_err(ha, hb));
   }
-  e->probe_err_decode = worst;
-  e->split_decode_ok = worst <= MLDHIP_PROBE_TOL;
+  probe_verdict(e, kProbeDecode, worst);
   return MLDHIP_OK;
 }
 
@@ -304,13 +307,8 @@ int probe_text(E* e, hipStream_t stream, ProbeRng& rng) {
   ProbeDev out;
   if (out.make((size_t)NP * W)) return e->fail(MLDHIP_EHIP, "range probe: hipMalloc");
   std::vector<float> ha, hb;
-  for (int split = 1; split >= 0; --split) {
-    e->text_split_ok = split != 0;
-    if (int rc = text_encode_impl(e, ids.data(), eos.data(), NP, out.p, stream, false)) return rc;
-    if (int rc = probe_down(e, stream, out.p, (size_t)NP * W, split ? ha : hb)) return rc;
-  }
-  e->probe_err_text = rel_err(ha, hb);
-  e->text_split_ok = e->probe_err_text <= MLDHIP_PROBE_TOL;
+  if (int rc = probe_pair(e, stream, kProbeText, out.p, (size_t)NP * W, ha, hb, [&](bool) { return text_encode_impl(e, ids.data(), eos.data(), NP, out.p, stream, false); })) return rc;
+  probe_verdict(e, kProbeText, rel_err(ha, hb));
   return MLDHIP_OK;
 }
 
@@ -324,7 +322,7 @@ int probe_eval(E* e, hipStream_t stream, ProbeRng& rng) {
   ProbeDev out;
   if (out.make((size_t)NB * kEvalOut)) return e->fail(MLDHIP_EHIP, "range probe: hipMalloc");
   std::vector<float> ha, hb;
-  if (e->group_ready[5] && e->cfg.max_frames >= kEvalUnit) {
+  if (e->group_ready[kGroupEvalMotion] && e->cfg.max_frames >= kEvalUnit) {
     const int T = std::min(64, e->cfg.max_frames);
     const int want[4] = {64, 37, 20, 4};
     std::vector<int32_t> lens(NB);
@@ -335,14 +333,10 @@ int probe_eval(E* e, hipStream_t stream, ProbeRng& rng) {
       for (size_t i = ((size_t)b * T + lens[b]) * NF; i < (size_t)(b + 1) * T * NF; ++i) hf[i] = 0.f;      // padded frames hold zeros, as the decoder leaves them
     ProbeDev feats;
     if (feats.up(hf)) return e->fail(MLDHIP_EHIP, "range probe: hipMalloc");
-    for (int split = 1; split >= 0; --split) {
-      e->eval_split_ok = split != 0;
-      if (int rc = t2m_motion_embed_impl(e, feats.p, lens.data(), NB, T, 0, out.p, stream, false)) return rc;
-      if (int rc = probe_down(e, stream, out.p, (size_t)NB * kEvalOut, split ? ha : hb)) return rc;
-    }
+    if (int rc = probe_pair(e, stream, kProbeEval, out.p, (size_t)NB * kEvalOut, ha, hb, [&](bool) { return t2m_motion_embed_impl(e, feats.p, lens.data(), NB, T, 0, out.p, stream, false); })) return rc;
     worst = std::max(worst, rel_err(ha, hb));
   }
-  if (e->group_ready[6]) {
+  if (e->group_ready[kGroupEvalText]) {
     const int L = std::min(20, e->cfg.t2m_max_words);
     const int want[4] = {L, 3, 2, 1};
     std::vector<int32_t> lens(NB);
@@ -352,11 +346,7 @@ int probe_eval(E* e, hipStream_t stream, ProbeRng& rng) {
     for (int i = 0; i < NB * L; ++i) hp[(size_t)i * kEvalPos + rng.bits() % kEvalPos] = 1.f;
     ProbeDev word, pos;
     if (word.up(hw) || pos.up(hp)) return e->fail(MLDHIP_EHIP, "range probe: hipMalloc");
-    for (int split = 1; split >= 0; --split) {
-      e->eval_split_ok = split != 0;
-      if (int rc = t2m_text_embed_impl(e, word.p, pos.p, lens.data(), NB, L, out.p, stream, false)) return rc;
-      if (int rc = probe_down(e, stream, out.p, (size_t)NB * kEvalOut, split ? ha : hb)) return rc;
-    }
+    if (int rc = probe_pair(e, stream, kProbeEval, out.p, (size_t)NB * kEvalOut, ha, hb, [&](bool) { return t2m_text_embed_impl(e, word.p, pos.p, lens.data(), NB, L, out.p, stream, false); })) return rc;
     worst = std::max(worst, rel_err(ha, hb));
   }
   // (c) the recurrent products by themselves: 16 seeded state rows (uniform in (-1, 1), where a GRU state lives) times W_hh^T of every loaded tower and direction,
@@ -364,7 +354,7 @@ int probe_eval(E* e, hipStream_t stream, ProbeRng& rng) {
   // gate terms O(1), and a W_hh whose split image has lost its precision (weights near 1e-5: both halves are half subnormals, ~4e-3 relative) then moves an embedding
   // by 1e-7 -- on a caller's rows whose input-side terms are as small as the recurrent ones it would not.  The product is held to the same bound as the outputs.
   for (int tower = 0; tower < 2; ++tower) {
-    if (!e->group_ready[5 + tower]) continue;
+    if (!e->group_ready[tower == 0 ? kGroupEvalMotion : kGroupEvalText]) continue;
     const int H = tower == 0 ? kEvalMotionH : kEvalTextH, M = 16;
     const std::string p = tower == 0 ? "t2m_motionencoder" : "t2m_textencoder";
     std::vector<float> hx((size_t)M * H);
@@ -373,17 +363,12 @@ int probe_eval(E* e, hipStream_t stream, ProbeRng& rng) {
     if (x.up(hx) || y.make((size_t)M * 3 * H)) return e->fail(MLDHIP_EHIP, "range probe: hipMalloc");
     for (int dir = 0; dir < 2; ++dir) {
       const float* W = P(e, p + (dir ? ".gru.weight_hh_l0_reverse" : ".gru.weight_hh_l0"));
-      for (int split = 1; split >= 0; --split) {
-        Ctx c{e, stream};
-        gemm_eval(c, lin_args(x.p, H, H, W, nullptr, y.p, 3 * H, M, 3 * H), split != 0);
-        if (c.rc) return c.rc;
-        if (int rc = probe_down(e, stream, y.p, (size_t)M * 3 * H, split ? ha : hb)) return rc;
-      }
+      auto run = [&](bool split) { Ctx c{e, stream}; gemm_eval(c, lin_args(x.p, H, H, W, nullptr, y.p, 3 * H, M, 3 * H), split); return c.rc; };      // (this GEMM takes its arithmetic as an argument, not from the flag)
+      if (int rc = probe_pair(e, stream, kProbeEval, y.p, (size_t)M * 3 * H, ha, hb, run)) return rc;
       worst = std::max(worst, rel_err(ha, hb));
     }
   }
-  e->probe_err_eval = worst;
-  e->eval_split_ok = worst < 0.f || worst <= MLDHIP_PROBE_TOL;
+  e->probe[kProbeEval] = {worst < 0.f || worst <= MLDHIP_PROBE_TOL, worst};
   return MLDHIP_OK;
 }
 
@@ -398,13 +383,8 @@ int probe_uestc(E* e, hipStream_t stream, ProbeRng& rng) {
   if (x.up(hx) || out.make((size_t)NB * (kStgFeat + NC))) return e->fail(MLDHIP_EHIP, "range probe: hipMalloc");
   const int64_t strides[4] = {(int64_t)kStgJoints * kStgIn * T, (int64_t)kStgIn * T, T, 1};
   std::vector<float> ha, hb;
-  for (int split = 1; split >= 0; --split) {
-    e->uestc_split_ok = split != 0;
-    if (int rc = uestc_recognize_impl(e, x.p, strides, NB, T, out.p + (size_t)NB * kStgFeat, out.p, stream, false)) return rc;
-    if (int rc = probe_down(e, stream, out.p, (size_t)NB * (kStgFeat + NC), split ? ha : hb)) return rc;
-  }
-  e->probe_err_uestc = rel_err(ha, hb);
-  e->uestc_split_ok = e->probe_err_uestc <= MLDHIP_PROBE_TOL;
+  if (int rc = probe_pair(e, stream, kProbeUestc, out.p, (size_t)NB * (kStgFeat + NC), ha, hb, [&](bool) { return uestc_recognize_impl(e, x.p, strides, NB, T, out.p + (size_t)NB * kStgFeat, out.p, stream, false); })) return rc;
+  probe_verdict(e, kProbeUestc, rel_err(ha, hb));
   return MLDHIP_OK;
 }
 
@@ -412,18 +392,18 @@ int range_probe(E* e, hipStream_t stream, const float* user_text, const float* u
   Scoped<bool> noise_off(e->noise_off, true);      // deterministic on every handle: the probe compares arithmetic on the eta = 0 step (include/mldhip.h "range_probe")
   ProbeRng rng;
   const bool user = user_text != nullptr && user_lat != nullptr && user_B > 0;      // "range_probe" 2: the reverse-loop stage alone, on the caller's batch
-  if (e->group_ready[0] && !is_novae(e))
+  if (e->group_ready[kGroupDenoiser] && !is_novae(e))
     if (int rc = probe_loop(e, stream, rng, user_text, user_lat, user ? user_B : 0)) return rc;
   if (user) { e->phase = 0; return MLDHIP_OK; }
-  if (e->group_ready[1] && !is_novae(e))
+  if (e->group_ready[kGroupVaeDecoder] && !is_novae(e))
     if (int rc = probe_decoder(e, stream, rng)) return rc;
-  if (e->group_ready[0] && is_novae(e))
+  if (e->group_ready[kGroupDenoiser] && is_novae(e))
     if (int rc = probe_novae(e, stream, rng)) return rc;
-  if (e->cfg.clip_layers > 0 && e->group_ready[4] && e->arena_x3)
+  if (e->cfg.clip_layers > 0 && e->group_ready[kGroupClip] && e->arena_x3)
     if (int rc = probe_text(e, stream, rng)) return rc;
-  if (e->cfg.t2m_eval && (e->group_ready[5] || e->group_ready[6]) && e->arena_x3)
+  if (e->cfg.t2m_eval && (e->group_ready[kGroupEvalMotion] || e->group_ready[kGroupEvalText]) && e->arena_x3)
     if (int rc = probe_eval(e, stream, rng)) return rc;
-  if (e->cfg.uestc_rec && e->group_ready[9] && e->uestc_tabs_x3)
+  if (e->cfg.uestc_rec && e->group_ready[kGroupUestc] && e->uestc_tabs_x3)
     if (int rc = probe_uestc(e, stream, rng)) return rc;
   e->phase = 0;
   return MLDHIP_OK;

@@ -1,7 +1,6 @@
 // The sampling drivers behind the C ABI: the single call (sample_impl), the coalesced and the pipelined form of mldhip_sample_many, the one-step
 // denoiser calls, the diffusion-only call, and the cluster loop's self-healing; the short host sequences they share are the helpers at the top.
-// Part of libmldhip's single translation unit (included by ../mldhip.hip, in this order: state, params, dispatch,
-// path_loop, streams, path_vae, path_latent, path_novae, path_clip, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace).
+// Part of libmldhip's single translation unit; include order: see mldhip.hip.  Internal linkage throughout (anonymous namespace).
 #pragma once
 
 namespace {
@@ -88,7 +87,7 @@ int sample_impl(E* e, const float* text_emb_dev, const int32_t* actions_host, co
                 const int32_t* lengths_host, int32_t B, float* latents_out_dev, float* feats_out_dev, float* joints_out_dev,
                 void* stream_) {
   if (!e->finalized) return e->fail(MLDHIP_ESTATE, "mldhip_sample before mldhip_finalize_weights");
-  if (!e->group_ready[0] || !e->group_ready[1] || (joints_out_dev && !e->group_ready[2]))
+  if (!e->group_ready[kGroupDenoiser] || !e->group_ready[kGroupVaeDecoder] || (joints_out_dev && !e->group_ready[kGroupStats]))
     return e->fail(MLDHIP_ESTATE, "mldhip_sample needs denoiser.*, vae.decoder.* (and mean/std for joints) loaded");
   if (!init_latents_dev) return e->fail(MLDHIP_EINVAL, "null input pointer");
   int T = 0;
@@ -97,7 +96,7 @@ int sample_impl(E* e, const float* text_emb_dev, const int32_t* actions_host, co
   heal_cluster(e);
   if (e->probe_first_call && text_emb_dev) {              // "range_probe" 2: the loop probe on THIS batch before it is sampled (one-off, synchronous)
     e->probe_first_call = false;
-    if (e->split_loop_ok)
+    if (e->probe[kProbeLoop].ok)
       if (int rc = range_probe(e, stream, text_emb_dev, init_latents_dev, B)) return rc;
   }
   CtxUse use(e, stream);                                  // picks + binds a workspace context (see WsContext)
@@ -471,7 +470,7 @@ int sample_many_impl(E* e, const mldhip_request* rq, int nreq, hipStream_t strea
     want_j = want_j || r.joints_out_dev;
     want_f = want_f || r.feats_out_dev || (r.joints_out_dev && !e->dec_lean);      // features for a caller (any request): the full [M][263] rows; joints alone do not need them ("dec_lean")
   }
-  if (!e->group_ready[0] || !e->group_ready[1] || (want_j && !e->group_ready[2]))
+  if (!e->group_ready[kGroupDenoiser] || !e->group_ready[kGroupVaeDecoder] || (want_j && !e->group_ready[kGroupStats]))
     return e->fail(MLDHIP_ESTATE, "mldhip_sample_many needs denoiser.*, vae.decoder.* (and mean/std for joints) loaded");
   bool want_t = false;
   for (int i = 0; traj && i < nreq; ++i) want_t = want_t || traj[i];
@@ -532,7 +531,7 @@ int sample_many_impl(E* e, const mldhip_request* rq, int nreq, hipStream_t strea
 // ---------------------------------------------------------------------------------------------------------------- one denoiser step; the diffusion-only call
 int denoiser_forward_impl(E* e, const float* sample_dev, int32_t timestep, const float* text_emb_dev,
                           const int32_t* actions_host, int32_t R, float* out_dev, void* stream_) {
-  if (!e->finalized || !e->group_ready[0]) return e->fail(MLDHIP_ESTATE, "denoiser_forward before finalize / denoiser.* not loaded");
+  if (!e->finalized || !e->group_ready[kGroupDenoiser]) return e->fail(MLDHIP_ESTATE, "denoiser_forward before finalize / denoiser.* not loaded");
   if (!sample_dev || !out_dev) return e->fail(MLDHIP_EINVAL, "null pointer");
   if (R < 1 || R > 2 * e->cfg.max_batch) return e->fail(MLDHIP_EINVAL, "R=%d outside [1, 2*max_batch]", R);
   if (timestep < 0 || timestep >= e->cfg.num_train_timesteps) return e->fail(MLDHIP_EINVAL, "timestep %d out of range", timestep);
@@ -562,7 +561,7 @@ int denoiser_forward_impl(E* e, const float* sample_dev, int32_t timestep, const
 
 int denoiser_forward_novae_impl(E* e, const float* sample_dev, int32_t timestep, const float* text_emb_dev,
                                 const int32_t* lengths_host, int32_t R, int32_t T, float* out_dev, void* stream_) {
-  if (!e->finalized || !e->group_ready[0]) return e->fail(MLDHIP_ESTATE, "denoiser_forward_novae before finalize / denoiser.* not loaded");
+  if (!e->finalized || !e->group_ready[kGroupDenoiser]) return e->fail(MLDHIP_ESTATE, "denoiser_forward_novae before finalize / denoiser.* not loaded");
   if (!sample_dev || !text_emb_dev || !lengths_host || !out_dev) return e->fail(MLDHIP_EINVAL, "null pointer");
   if (R < 1 || R > 2 * e->cfg.max_batch) return e->fail(MLDHIP_EINVAL, "R=%d outside [1, 2*max_batch]", R);
   if (T < 1 || T > e->cfg.max_frames) return e->fail(MLDHIP_EINVAL, "T=%d outside [1, max_frames=%d]", T, e->cfg.max_frames);
@@ -587,7 +586,7 @@ int denoiser_forward_novae_impl(E* e, const float* sample_dev, int32_t timestep,
 
 int sample_novae_impl(E* e, const float* text_emb_dev, const float* init_latents_dev, const int32_t* lengths_host,
                       int32_t B, const float* step_noise_dev, uint64_t seed, float* feats_out_dev, float* joints_out_dev, void* stream_) {
-  if (!e->finalized || !e->group_ready[0] || (joints_out_dev && !e->group_ready[2]))
+  if (!e->finalized || !e->group_ready[kGroupDenoiser] || (joints_out_dev && !e->group_ready[kGroupStats]))
     return e->fail(MLDHIP_ESTATE, "mldhip_sample_novae needs finalize and denoiser.* (and mean/std for joints) loaded");
   if (!text_emb_dev || !init_latents_dev) return e->fail(MLDHIP_EINVAL, "null input pointer");
   int T = 0;

@@ -1,11 +1,33 @@
 // Engine state: parameter table entries, per-layer weight views, workspace contexts, the handle struct.
-// Part of libmldhip's single translation unit (included by ../mldhip.hip, in this order: state, params, dispatch,
-// path_loop, streams, path_vae, path_latent, path_novae, path_clip, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace) except the handle type itself.
+// Part of libmldhip's single translation unit; include order: see mldhip.hip.  Internal linkage throughout (anonymous namespace) except the handle type itself.
 #pragma once
 
 namespace {
 
 std::string g_last_error;   // for failures before a handle exists
+
+// Weight groups: loaded completely or not at all (mldhip_finalize_weights); an entry point asks for those it reads.  Key -> group: kGroupRules (engine/params.hpp).  Optional modules last.
+enum WeightGroup {
+  kGroupDenoiser,     // denoiser.*
+  kGroupVaeDecoder,   // vae.* but the encoder's tensors
+  kGroupStats,        // dataset statistics: mean, std (and any key no rule names)
+  kGroupVaeEncoder,   // vae.encoder.*, vae.skel_embedding.*, vae.global_motion_token, vae.query_pos_encoder.*
+  kGroupClip,         // CLIP text tower (clip_layers > 0): text_encoder.*
+  kGroupEvalMotion,   // T2M motion evaluators (t2m_eval = 1): t2m_moveencoder.*, t2m_motionencoder.*, mean_eval, std_eval
+  kGroupEvalText,     // T2M text evaluator (t2m_eval = 1): t2m_textencoder.*
+  kGroupSmpl,         // SMPL body model (smpl_verts > 0): smpl.*
+  kGroupA2m,          // HumanAct12 recognition GRU (a2m_rec = 1): a2m_rec.*
+  kGroupUestc,        // UESTC recognition ST-GCN (uestc_rec = 1): uestc_rec.*
+  kGroupCount
+};
+constexpr bool optional_group(WeightGroup g) { return g >= kGroupClip; }
+
+// Range probe (engine/probe.hpp): one verdict per stage -- the reverse loop; decoder / encoder / diffusion-only GEMMs and attention; the half-Q|K|V form of the decoder's
+// self-attention block ("dec_half", held to MLDHIP_PROBE_TOL_HALF); the CLIP text tower; the T2M evaluator towers (GEMMs and the recurrence); the UESTC recognition ST-GCN.
+// ok = false: the stage runs on exact-fp32 MFMAs although the handle was created in the split mode (kProbeDecodeHalf: the decoder keeps fp32 Q | K | V and x3 products);
+// err: the stage's reading, max-abs difference / max-abs reference (-1: not probed / no such module)
+enum ProbeStage { kProbeLoop, kProbeDecode, kProbeDecodeHalf, kProbeText, kProbeEval, kProbeUestc, kProbeStages };
+struct ProbeVerdict { bool ok = true; float err = -1.f; };
 
 struct Param {
   std::string key;
@@ -13,8 +35,7 @@ struct Param {
   size_t offset = 0;   // floats into the arena
   size_t numel = 0;
   bool loaded = false;
-  int group = 0;       // 0 denoiser, 1 vae decoder, 2 dataset statistics, 3 vae encoder, 4 CLIP text tower, 5 T2M motion evaluators (+ mean_eval / std_eval), 6 T2M text evaluator, 7 SMPL body model,
-                       // 8 HumanAct12 recognition GRU, 9 UESTC recognition ST-GCN
+  WeightGroup group = kGroupStats;
 };
 
 struct EncLayerP {   // TransformerEncoderLayer (cross_attention.py:236-272)
@@ -80,9 +101,7 @@ struct mldhip_engine {
   int device = 0;
   std::string err;
   bool finalized = false;
-  static constexpr int kGroups = 10;
-  bool group_ready[kGroups] = {false, false, false, false, false, false, false, false, false, false};   // denoiser, vae decoder, mean/std, vae encoder, CLIP text tower (clip_layers > 0), T2M motion / text evaluators (t2m_eval = 1), SMPL body model (smpl_verts > 0),
-                                                                                                 // HumanAct12 recognition GRU (a2m_rec = 1), UESTC recognition ST-GCN (uestc_rec = 1)
+  bool group_ready[kGroupCount] = {};
 
   // ---- parameters
   std::vector<Param> params;
@@ -218,17 +237,7 @@ struct mldhip_engine {
   int range_probe = 1;       // "range_probe": finalize compares the split-f16 kernels with the exact-fp32 ones on a probe batch and falls back per stage
 #endif
   bool probe_first_call = false; // "range_probe" 2: the next text-conditioned mldhip_sample runs the reverse-loop probe on its own batch first
-  bool split_loop_ok = true;     // false: the reverse loop runs on exact-fp32 MFMAs although the handle was created in the split mode
-  bool split_decode_ok = true;   // false: decoder / encoder / diffusion-only GEMMs and attention run on exact-fp32 MFMAs
-  bool dec_half_ok = true;       // false: the probe read the half-Q|K|V form of the decoder's self-attention block above MLDHIP_PROBE_TOL_HALF: the decoder keeps fp32 Q | K | V and x3 products
-  float probe_err_decode_half = -1.f;
-  bool text_split_ok = true;     // false: the CLIP text tower (engine/path_clip.hpp) runs its GEMMs and attention on exact-fp32 MFMAs
-  float probe_err_text = -1.f;   // the tower stage's reading (-1: not probed / no tower)
-  bool eval_split_ok = true;     // false: the T2M evaluator towers (engine/path_eval.hpp) run their GEMMs and the recurrence on exact-fp32 MFMAs
-  float probe_err_eval = -1.f;   // the evaluator stage's reading (-1: not probed / no evaluators)
-  bool uestc_split_ok = true;    // false: the UESTC recognition ST-GCN (engine/path_uestc.hpp) runs its GEMMs on exact-fp32 MFMAs
-  float probe_err_uestc = -1.f;  // that stage's reading (-1: not probed / no net)
-  float probe_err_loop = -1.f, probe_err_decode = -1.f;   // probe results (max-abs difference / max-abs reference); -1: not probed
+  ProbeVerdict probe[kProbeStages];   // reset by every finalize, written by the stages of engine/probe.hpp
   unsigned* nonfinite = nullptr; // device counter: non-finite values seen in the latents / joints a sample call produced (sticky until read)
 
   int launches[3] = {0, 0, 0};

@@ -1,7 +1,5 @@
 // Finalize-time derived weight images: the item streams of the persistent loop, the cluster loop and the decoder / encoder row-strip kernels.
-// Part of libmldhip's single translation unit (included by ../mldhip.hip, in this order: state, params, dispatch,
-// path_loop, streams, path_vae, path_latent, path_novae, path_clip, graphs, create, serve, probe).  Internal linkage throughout (anonymous namespace)
-// except the handle type itself.
+// Part of libmldhip's single translation unit; include order: see mldhip.hip.  Internal linkage throughout (anonymous namespace) except the handle type itself.
 #pragma once
 
 namespace {
@@ -52,7 +50,7 @@ void push_ffn(ItemList<LoopItem>& items, const float* w1, const float* w2, int F
 int build_loop_stream(Ctx& c) {
   E* e = c.e;
   e->loop_ips = 0;
-  if (!fused_built(e) || !e->group_ready[0]) return 0;
+  if (!fused_built(e) || !e->group_ready[kGroupDenoiser]) return 0;
   const int L = e->cfg.num_layers, nb = (L - 1) / 2, n = e->cfg.num_inference_steps, F = e->cfg.ff_size;
   ItemList<LoopItem> items{e->arena};
   // chunk-major inside a group: the items that multiply the same 32 columns of A are adjacent (loop_fused.hpp run2 / run3)
@@ -125,7 +123,7 @@ int build_loop_stream(Ctx& c) {
 int build_cluster_stream(Ctx& c) {
   E* e = c.e;
   if (e->cl_stream) { (void)hipFree(e->cl_stream); e->cl_stream = nullptr; }
-  if (!fused_built(e) || !e->group_ready[0] || !e->loop_ips || e->cfg.precision != MLDHIP_PREC_F16X3) return 0;
+  if (!fused_built(e) || !e->group_ready[kGroupDenoiser] || !e->loop_ips || e->cfg.precision != MLDHIP_PREC_F16X3) return 0;
   const int L = e->cfg.num_layers, nb = (L - 1) / 2, F = e->cfg.ff_size;
   ItemList<ClFrag> frags{e->arena};
   // Ph1 and the out-projection of head hc, the same in both forms: waves 0-3 [Q, K], waves 4-7 [V]; then the head's K slice of the out-projection:
@@ -191,8 +189,8 @@ int build_ffn_streams(Ctx& c) {
   const bool split = e->cfg.precision == MLDHIP_PREC_F16X3;
   if (!split || is_novae(e) || e->cfg.latent_dim != 256 || e->cfg.ff_size != 1024) return 0;
   std::vector<std::pair<const float*, const float*>> layers;
-  if (e->group_ready[1]) for (auto& L : e->dec) layers.push_back({L.l1_w, L.l2_w});
-  if (e->group_ready[3]) for (auto& L : e->venc) layers.push_back({L.l1_w, L.l2_w});
+  if (e->group_ready[kGroupVaeDecoder]) for (auto& L : e->dec) layers.push_back({L.l1_w, L.l2_w});
+  if (e->group_ready[kGroupVaeEncoder]) for (auto& L : e->venc) layers.push_back({L.l1_w, L.l2_w});
   if (layers.empty()) return 0;
   ItemList<LoopItem> items{e->arena};
   for (auto& lw : layers) push_ffn(items, lw.first, lw.second, 1024);
@@ -206,11 +204,11 @@ int build_ffn_streams(Ctx& c) {
           for (int cb = 0; cb < 2; ++cb) items.push(w, K, (2 * pr + cb) * 128, sg * 256 + kc * 32);
   };
   const int nbv = (e->cfg.num_layers - 1) / 2;
-  if (e->group_ready[1]) {
+  if (e->group_ready[kGroupVaeDecoder]) {
     for (auto& L : e->dec) { gstream(L.in_w, 768, 256); gstream(L.out_w, 256, 256); }
     if (!is_actor(e)) for (int i = 0; i < nbv; ++i) gstream(P(e, "vae.decoder.linear_blocks." + std::to_string(i) + ".weight"), 256, 512);
   }
-  if (e->group_ready[3]) {
+  if (e->group_ready[kGroupVaeEncoder]) {
     for (auto& L : e->venc) { gstream(L.in_w, 768, 256); gstream(L.out_w, 256, 256); }
     if (!is_actor(e)) for (int i = 0; i < nbv; ++i) gstream(P(e, "vae.encoder.linear_blocks." + std::to_string(i) + ".weight"), 256, 512);
   }
@@ -219,7 +217,7 @@ int build_ffn_streams(Ctx& c) {
   // 128 < NF < 256 (KIT-ML: 251): two blocks, per chunk [block 0, 1] (final_strip2_x3_kernel)
   const size_t final_first = items.size();
   const int NFv = e->cfg.nfeats, final_blocks = final_strip_blocks(e);
-  if (e->group_ready[1] && final_blocks) {
+  if (e->group_ready[kGroupVaeDecoder] && final_blocks) {
     const float* wf = P(e, "vae.final_layer.weight");
     for (int kc = 0; kc < 8; ++kc)
       for (int blk = 0; blk < final_blocks; ++blk) items.push(wf, 256, blk * 128, kc * 32, std::min(128, NFv - blk * 128));

@@ -10,12 +10,25 @@
 //   sample()     ~2.1k kernel launches captured once per (B, Tmax, requested outputs) and workspace context into a
 //                hipGraph and replayed: the 50-step loop has no host work and no host<->device sync.
 //
-// Source layout: engine/state.hpp (handle, contexts) -> engine/params.hpp (weight contract, schedules) ->
-// engine/dispatch.hpp (kernel selection, the counted launch) -> engine/path_loop.hpp (the latent models' reverse loop) -> engine/streams.hpp (finalize-time weight
-// images) -> engine/path_vae.hpp (VAE decode / encode, feats2joints) -> engine/path_latent.hpp / engine/path_novae.hpp / engine/path_clip.hpp / engine/path_eval.hpp / engine/path_smpl.hpp / engine/path_a2m.hpp / engine/path_uestc.hpp / engine/path_metrics.hpp (the sample calls, the text tower, the T2M evaluator towers, the SMPL body model, the HumanAct12 recognition GRU, the UESTC recognition ST-GCN, the text-to-motion metric kernels) ->
-// engine/graphs.hpp (graph capture and caches) -> engine/create.hpp (validation, workspace carve, LDS registration, teardown) ->
-// engine/serve.hpp (the sampling drivers and their shared host sequences) -> engine/probe.hpp (range probe) -> the C ABI below: each
-// entry point is its argument checks and a call into the engine.  kernels/*.hpp hold the device code (no __global__ in this file).
+// Source layout, in include order; then the C ABI below: each entry point is its argument checks and a call into the engine.  kernels/*.hpp hold the device code (no __global__ in this file).
+//   engine/state.hpp         handle, contexts, weight groups, probe verdicts
+//   engine/params.hpp        weight contract, schedules
+//   engine/dispatch.hpp      kernel selection, the counted launch
+//   engine/path_loop.hpp     the latent models' reverse loop
+//   engine/streams.hpp       finalize-time weight images
+//   engine/path_vae.hpp      VAE decode / encode, feats2joints
+//   engine/path_latent.hpp   the latent models' sample calls
+//   engine/path_novae.hpp    the diffusion-only variant's sample calls
+//   engine/path_clip.hpp     the CLIP text tower
+//   engine/path_eval.hpp     the T2M evaluator towers
+//   engine/path_smpl.hpp     the SMPL body model
+//   engine/path_a2m.hpp      the HumanAct12 recognition GRU
+//   engine/path_uestc.hpp    the UESTC recognition ST-GCN
+//   engine/path_metrics.hpp  the text-to-motion metric kernels
+//   engine/graphs.hpp        graph capture and caches
+//   engine/create.hpp        validation and defaults, workspace carve, LDS registration, teardown
+//   engine/serve.hpp         the sampling drivers and their shared host sequences
+//   engine/probe.hpp         range probe
 // One translation unit: hipcc builds it in one pass for gfx950.
 //
 // Reference call stack being replaced: mld/models/modeltype/mld.py:216-265,290-360.
@@ -79,8 +92,13 @@ using namespace mld;
 #include "engine/probe.hpp"
 #include "kernels/ddim_step.hpp"   // (last on purpose: see the file)
 
-
 // ======================================================================================= C ABI
+
+// Struct sizes a caller may pass.  Fields were appended over time, some without a new ABI number: a caller built before an append passes the struct that ends
+// behind the last field it knows, and what it does not cover keeps its default (the module is off; a numeric_info field is not written).
+#define MLDHIP_ENDS_BEHIND(T, field) (int32_t)(offsetof(T, field) + sizeof(T::field))
+template <size_t N>
+static bool size_accepted(const int32_t (&sizes)[N], int32_t size) { return std::find(sizes, sizes + N, size) != sizes + N; }
 
 extern "C" {
 
@@ -99,12 +117,7 @@ void mldhip_default_config(mldhip_config* c) {
   c->max_in_flight = 1;
   // no text tower by default (clip_layers 0); the other fields are CLIP ViT-L/14's, clip_max_prompts 0 = 2 x max_batch
   c->clip_layers = 0; c->clip_heads = 12; c->clip_ff = 3072; c->clip_vocab = 49408; c->clip_ctx = 77; c->clip_max_prompts = 0;
-  // no T2M evaluator towers by default (t2m_eval 0); t2m_max_motions 0 = 2 x max_batch, t2m_max_words 0 = 32
-  c->t2m_eval = 0; c->t2m_max_motions = 0; c->t2m_max_words = 0;
-  c->smpl_verts = 0;      // no SMPL body model by default
-  c->a2m_rec = 0; c->a2m_max_motions = 0;      // no recognition GRU by default; a2m_max_motions 0 = 4 x max_batch
-  c->uestc_rec = 0; c->uestc_max_motions = 0; c->uestc_classes = 0;      // no recognition ST-GCN by default; uestc_max_motions 0 = 2 x max_batch, uestc_classes 0 = 40
-  c->t2m_metrics = 0; c->metrics_max_rows = 0;      // no metric kernels by default; metrics_max_rows 0 = 8192
+  // every other optional module is off by default and its capacities are 0 = the defaults of resolve_defaults (engine/create.hpp): all zero bits, as the memset left them
 }
 
 const char* mldhip_last_error(mldhip_handle* h) { return h ? h->err.c_str() : g_last_error.c_str(); }
@@ -112,32 +125,24 @@ const char* mldhip_last_error(mldhip_handle* h) { return h ? h->err.c_str() : g_
 int mldhip_create(const mldhip_config* cfg, int device, mldhip_handle** out) {
   auto bad = [&](const char* m) { g_last_error = m; return MLDHIP_EINVAL; };
   if (!cfg || !out) return bad("null argument");
-  // ABI 6 appended `eta`: a caller built against ABI 5 passes the smaller struct (eta is 0 then); the fields are read from a full-size copy
-  // ABI 7 appended the clip_* fields: a caller built against ABI 6 passes the struct that ends behind eta (no text tower then)
-  // the t2m_* fields came behind the clip_* fields without a new ABI number: a caller built before them passes the struct that ends behind clip_max_prompts (no evaluators then)
-  constexpr int32_t kCfgAbi5 = (int32_t)offsetof(mldhip_config, eta), kCfgAbi6 = (int32_t)offsetof(mldhip_config, clip_layers), kCfgNoEval = (int32_t)offsetof(mldhip_config, t2m_eval);
-  // ... and smpl_verts behind the t2m_* fields, the same way: the struct that ends behind t2m_max_words means no body model
-  constexpr int32_t kCfgNoSmpl = (int32_t)offsetof(mldhip_config, smpl_verts);
-  // ... and the a2m_* fields behind smpl_verts: the struct that ends behind smpl_verts means no recognizer
-  constexpr int32_t kCfgNoA2m = (int32_t)offsetof(mldhip_config, a2m_rec);
-  // ... and the uestc_* fields behind them: the struct that ends behind a2m_max_motions means no recognition ST-GCN
-  constexpr int32_t kCfgNoUestc = (int32_t)offsetof(mldhip_config, uestc_rec);
-  // ... and the two metric fields behind those: the struct that ends behind uestc_classes means no metric kernels
-  constexpr int32_t kCfgNoMetrics = (int32_t)offsetof(mldhip_config, t2m_metrics);
-  if (cfg->struct_size != (int32_t)sizeof(mldhip_config) && cfg->struct_size != kCfgAbi5 && cfg->struct_size != kCfgAbi6 && cfg->struct_size != kCfgNoEval && cfg->struct_size != kCfgNoSmpl &&
-      cfg->struct_size != kCfgNoA2m && cfg->struct_size != kCfgNoUestc && cfg->struct_size != kCfgNoMetrics) return bad("mldhip_config.struct_size mismatch (ABI skew)");
+  constexpr int32_t kConfigAbi5 = MLDHIP_ENDS_BEHIND(mldhip_config, max_in_flight);
+  constexpr int32_t kConfigSizes[] = {
+      kConfigAbi5,                                              // ABI 5 caller: no eta (it is 0 then, whatever the default)
+      MLDHIP_ENDS_BEHIND(mldhip_config, eta),                   // ABI 6 caller: no text tower
+      MLDHIP_ENDS_BEHIND(mldhip_config, clip_max_prompts),      // ABI 7 caller from before the t2m_* fields: no evaluators
+      MLDHIP_ENDS_BEHIND(mldhip_config, t2m_max_words),         // ... from before smpl_verts: no body model
+      MLDHIP_ENDS_BEHIND(mldhip_config, smpl_verts),            // ... from before the a2m_* fields: no recognition GRU
+      MLDHIP_ENDS_BEHIND(mldhip_config, a2m_max_motions),       // ... from before the uestc_* fields: no recognition ST-GCN
+      MLDHIP_ENDS_BEHIND(mldhip_config, uestc_classes),         // ... from before the two metric fields: no metric kernels
+      (int32_t)sizeof(mldhip_config),                           // today's caller
+  };
+  if (!size_accepted(kConfigSizes, cfg->struct_size)) return bad("mldhip_config.struct_size mismatch (ABI skew)");
   mldhip_config full;
   mldhip_default_config(&full);                       // fields the caller's struct does not cover keep their defaults ...
-  if (cfg->struct_size == kCfgAbi5) full.eta = 0.0f;
+  if (cfg->struct_size == kConfigAbi5) full.eta = 0.0f;
   std::memcpy(&full, cfg, (size_t)cfg->struct_size);  // ... every field it covers is the caller's
   full.struct_size = (int32_t)sizeof(mldhip_config);
-  if (full.clip_layers > 0 && full.clip_max_prompts == 0) full.clip_max_prompts = 2 * full.max_batch;
-  if (full.t2m_eval && full.t2m_max_motions == 0) full.t2m_max_motions = 2 * full.max_batch;
-  if (full.t2m_eval && full.t2m_max_words == 0) full.t2m_max_words = 32;
-  if (full.a2m_rec && full.a2m_max_motions == 0) full.a2m_max_motions = 4 * full.max_batch;
-  if (full.uestc_rec && full.uestc_max_motions == 0) full.uestc_max_motions = 2 * full.max_batch;
-  if (full.uestc_rec && full.uestc_classes == 0) full.uestc_classes = 40;
-  if (full.t2m_metrics && full.metrics_max_rows == 0) full.metrics_max_rows = 8192;
+  resolve_defaults(full);
   if (const char* what = config_error(&full)) return bad(what);
   int num_cus = 0;
   if (int rc = check_device(device, &num_cus)) return rc;
@@ -154,13 +159,7 @@ int mldhip_load_tensor(mldhip_handle* e, const char* key, const void* data, cons
   DeviceGuard dg(e->device);
   if (dtype != MLDHIP_F32) return e->fail(MLDHIP_EINVAL, "tensor %s: only float32 tensors are accepted", key);
   auto it = e->index.find(key);
-  if (it == e->index.end()) {
-    static const char* ignorable[] = {
-                                      "denoiser.mem_pos.", "text_encoder.", "t2m_", "vae.dist_layer.", "smpl.", "a2m_rec.", "uestc_rec."};
-    for (auto p : ignorable)
-      if (std::strncmp(key, p, std::strlen(p)) == 0) return 1;
-    return e->fail(MLDHIP_EINVAL, "unexpected key %s", key);
-  }
+  if (it == e->index.end()) return ignorable_key(key) ? 1 : e->fail(MLDHIP_EINVAL, "unexpected key %s", key);
   Param& p = e->params[it->second];
   size_t numel = 1;
   for (int i = 0; i < ndim; ++i) numel *= size_t(shape[i]);
@@ -254,7 +253,7 @@ int mldhip_set_option(mldhip_handle* e, const char* name, int64_t value) {
   } else if (n == "dec_half") {
     if (value < 0 || value > 6 || value == 3 || value == 5) return e->fail(MLDHIP_EINVAL, "dec_half must be 0 (fp32 Q|K|V, split x3 products), 1 (half Q|K|V; strip height by launch size), 4 or 6 (1 with 64- / 96-row in-projection strips always) or 2 (1, but never overruled by finalize's probe)");
     // the probe's reading of the form is part of finalize: switching it on (with the veto in force) on a probed handle that has not read it asks for finalize again
-    if (value != 0 && value != 2 && e->finalized && e->range_probe && e->cfg.precision == MLDHIP_PREC_F16X3 && e->probe_err_decode >= 0.f && e->probe_err_decode_half < 0.f) e->finalized = false;
+    if (value != 0 && value != 2 && e->finalized && e->range_probe && e->cfg.precision == MLDHIP_PREC_F16X3 && e->probe[kProbeDecode].err >= 0.f && e->probe[kProbeDecodeHalf].err < 0.f) e->finalized = false;
     e->dec_half = (int)value;
   } else if (n == "tile_x3") {
     if (value != 0 && value != 1) return e->fail(MLDHIP_EINVAL, "tile_x3 must be 0 or 1");
@@ -302,15 +301,13 @@ int mldhip_missing_keys(mldhip_handle* e, char* buf, int64_t buflen) {
 int mldhip_finalize_weights(mldhip_handle* e, void* stream_) {
   if (!e) return MLDHIP_EINVAL;
   DeviceGuard dg(e->device);
-  // A group (denoiser / vae decoder / mean+std) must be loaded completely or not at all; ops of an
-  // absent group fail with MLDHIP_ESTATE, sample() needs all three.
-  constexpr int NG = mldhip_engine::kGroups;
-  int have[NG] = {0}, total[NG] = {0}, any = 0;
+  // A weight group (engine/state.hpp) must be loaded completely or not at all; ops of an absent group fail with MLDHIP_ESTATE
+  int have[kGroupCount] = {0}, total[kGroupCount] = {0}, any = 0;
   for (auto& p : e->params) { total[p.group]++; have[p.group] += p.loaded; any += p.loaded; }
   for (auto& p : e->params)
     if (!p.loaded && have[p.group] != 0) return e->fail(MLDHIP_ENOKEY, "missing tensor %s (strict load)", p.key.c_str());
   if (any == 0) return e->fail(MLDHIP_ENOKEY, "no tensors loaded");
-  for (int g = 0; g < NG; ++g) e->group_ready[g] = total[g] > 0 && have[g] == total[g];
+  for (int g = 0; g < kGroupCount; ++g) e->group_ready[g] = total[g] > 0 && have[g] == total[g];
   hipStream_t stream = (hipStream_t)stream_;
   bind_layers(e);
   Ctx c{e, stream};
@@ -331,7 +328,7 @@ int mldhip_finalize_weights(mldhip_handle* e, void* stream_) {
   if (int rc = build_uestc_tables(c)) return rc;
   for (int k = 0; k < (int)e->ctxs.size(); ++k) {       // the derived tables live in each context's workspace
   bind_context(e, k);
-  if (e->group_ready[0]) {
+  if (e->group_ready[kGroupDenoiser]) {
     // PE-folded biases: token 1 (time) gets pe[1], token 2 (text) gets pe[2] (mld_denoiser.py:187,196)
     // (trans_dec: the memory tokens [time, text] get mem_pos.pe[0], pe[1] instead, mld_denoiser.py:213)
     const float* pe_time = is_novae(e) ? P(e, "denoiser.mem_pos.pe") : P(e, "denoiser.query_pos.pe") + D;
@@ -354,7 +351,7 @@ int mldhip_finalize_weights(mldhip_handle* e, void* stream_) {
       if (check_launch(c, "pad_cols")) return c.rc;
     }
   }
-  if (e->group_ready[3]) {
+  if (e->group_ready[kGroupVaeEncoder]) {
     const int NF = e->cfg.nfeats, KP = (NF + 31) / 32 * 32;
     MLD_LAUNCH(pad_cols_kernel, dim3((D * KP + 255) / 256), dim3(256), 0, stream,
                P(e, is_actor(e) ? "vae.encoder.skel_embedding.weight" : "vae.skel_embedding.weight"), e->WskelP, D, NF, KP);
@@ -371,8 +368,7 @@ int mldhip_finalize_weights(mldhip_handle* e, void* stream_) {
   if (e->loop_kernel == 3 && !e->loop_ips)      // (set before finalize: refused here, like mldhip_set_option refuses it afterwards)
     return e->fail(MLDHIP_EINVAL, "loop_kernel 3: the sample-major loop is built for fp32 / split-f16 loop arithmetic, latent_dim 256, ff_size 1024, 4 heads");
   e->finalized = true;
-  e->split_loop_ok = e->split_decode_ok = e->dec_half_ok = e->text_split_ok = e->eval_split_ok = e->uestc_split_ok = true;
-  e->probe_err_loop = e->probe_err_decode = e->probe_err_decode_half = e->probe_err_text = e->probe_err_eval = e->probe_err_uestc = -1.f;
+  for (ProbeVerdict& v : e->probe) v = ProbeVerdict{};
   if (e->cfg.precision == MLDHIP_PREC_F16X3 && e->range_probe) {
     if (int rc = range_probe(e, stream)) { e->finalized = false; return rc; }
     e->probe_first_call = e->range_probe == 2;
@@ -382,11 +378,13 @@ int mldhip_finalize_weights(mldhip_handle* e, void* stream_) {
 
 int mldhip_numeric_status(mldhip_handle* e, mldhip_numeric_info* out) {
   if (!e || !out) return MLDHIP_EINVAL;
-  // ABI 8 appended the text tower's two fields: a caller built against ABI 7 passes the struct that ends behind `reserved` and gets the fields it knows
-  // ... and the evaluator towers' two fields came behind them: the struct that ends behind probe_err_text is accepted too
-  constexpr int32_t kInfoAbi7 = (int32_t)offsetof(mldhip_numeric_info, text_split_ok), kInfoNoEval = (int32_t)offsetof(mldhip_numeric_info, eval_split_ok);
-  constexpr int32_t kInfoNoUestc = (int32_t)offsetof(mldhip_numeric_info, uestc_split_ok);      // ... and the recognition ST-GCN's two behind those
-  if (out->struct_size != (int32_t)sizeof(mldhip_numeric_info) && out->struct_size != kInfoAbi7 && out->struct_size != kInfoNoEval && out->struct_size != kInfoNoUestc) return e->fail(MLDHIP_EINVAL, "mldhip_numeric_info.struct_size mismatch (ABI)");
+  constexpr int32_t kInfoSizes[] = {
+      MLDHIP_ENDS_BEHIND(mldhip_numeric_info, reserved),        // ABI 7 caller: no text tower fields
+      MLDHIP_ENDS_BEHIND(mldhip_numeric_info, probe_err_text),  // ABI 8 caller from before the evaluator towers' two fields
+      MLDHIP_ENDS_BEHIND(mldhip_numeric_info, probe_err_eval),  // ... from before the recognition ST-GCN's two
+      (int32_t)sizeof(mldhip_numeric_info),                     // today's caller
+  };
+  if (!size_accepted(kInfoSizes, out->struct_size)) return e->fail(MLDHIP_EINVAL, "mldhip_numeric_info.struct_size mismatch (ABI)");
   DeviceGuard dg(e->device);
   HIP_TRY(e, hipDeviceSynchronize());
   unsigned n = 0;
@@ -395,28 +393,25 @@ int mldhip_numeric_status(mldhip_handle* e, mldhip_numeric_info* out) {
   // a cluster launch that ran into its wait bound poisoned its latents (counted above) and left its status word set: the handle stays off the cluster loop from here on
   // (the captured graphs that hold it are dropped); mldhip_set_option("loop_kernel", 4) re-arms it
   if (!e->cluster_failed && cluster_timed_out(e)) leave_cluster_loop(e);
-  out->probed = e->probe_err_loop >= 0.f || e->probe_err_decode >= 0.f || e->probe_err_text >= 0.f || e->probe_err_eval >= 0.f || e->probe_err_uestc >= 0.f;
-  out->loop_split_ok = e->cfg.precision == MLDHIP_PREC_F16X3 && e->split_loop_ok;
-  out->decode_split_ok = e->cfg.precision == MLDHIP_PREC_F16X3 && e->split_decode_ok;
-  out->probe_err_loop = e->probe_err_loop;
-  out->probe_err_decode = e->probe_err_decode;
-  out->nonfinite_values = (int64_t)n;
-  out->cluster_loop = !e->cl_stream ? 0 : e->cluster_foreign ? 3 : e->cluster_failed ? 2 : 1;
-  out->reserved = 0;
-  out->decode_half_ok = e->cfg.precision == MLDHIP_PREC_F16X3 && e->split_decode_ok && e->dec_half && (e->dec_half_ok || e->dec_half == 2);
-  out->probe_err_decode_half = e->probe_err_decode_half;
-  if (out->struct_size > kInfoAbi7) {
-    out->text_split_ok = e->cfg.clip_layers > 0 && e->cfg.precision == MLDHIP_PREC_F16X3 && e->arena_x3 && e->text_split_ok;
-    out->probe_err_text = e->probe_err_text;
-  }
-  if (out->struct_size > kInfoNoEval) {
-    out->eval_split_ok = e->cfg.t2m_eval && e->cfg.precision == MLDHIP_PREC_F16X3 && e->arena_x3 && e->eval_split_ok;
-    out->probe_err_eval = e->probe_err_eval;
-  }
-  if (out->struct_size > kInfoNoUestc) {
-    out->uestc_split_ok = uestc_x3(e) && e->group_ready[9];
-    out->probe_err_uestc = e->probe_err_uestc;
-  }
+  const bool x3 = e->cfg.precision == MLDHIP_PREC_F16X3;
+  const ProbeVerdict* v = e->probe;
+  mldhip_numeric_info full = {out->struct_size};
+  for (int s = 0; s < kProbeStages; ++s) full.probed |= v[s].err >= 0.f;      // (kProbeDecodeHalf is read only where kProbeDecode is)
+  full.loop_split_ok = x3 && v[kProbeLoop].ok;
+  full.decode_split_ok = x3 && v[kProbeDecode].ok;
+  full.probe_err_loop = v[kProbeLoop].err;
+  full.probe_err_decode = v[kProbeDecode].err;
+  full.nonfinite_values = (int64_t)n;
+  full.cluster_loop = !e->cl_stream ? 0 : e->cluster_foreign ? 3 : e->cluster_failed ? 2 : 1;
+  full.decode_half_ok = x3 && v[kProbeDecode].ok && e->dec_half && (v[kProbeDecodeHalf].ok || e->dec_half == 2);
+  full.probe_err_decode_half = v[kProbeDecodeHalf].err;
+  full.text_split_ok = e->cfg.clip_layers > 0 && x3 && e->arena_x3 && v[kProbeText].ok;
+  full.probe_err_text = v[kProbeText].err;
+  full.eval_split_ok = e->cfg.t2m_eval && x3 && e->arena_x3 && v[kProbeEval].ok;
+  full.probe_err_eval = v[kProbeEval].err;
+  full.uestc_split_ok = uestc_x3(e) && e->group_ready[kGroupUestc];
+  full.probe_err_uestc = v[kProbeUestc].err;
+  std::memcpy(out, &full, (size_t)out->struct_size);      // the caller gets the fields its struct covers
   return MLDHIP_OK;
 }
 
@@ -609,7 +604,7 @@ int mldhip_vae_decode(mldhip_handle* e, const float* z_dev, const int32_t* lengt
                       void* stream_) {
   if (!e) return MLDHIP_EINVAL;
   DeviceGuard dg(e->device);
-  if (!e->finalized || !e->group_ready[1]) return e->fail(MLDHIP_ESTATE, "vae_decode before finalize / vae.* not loaded");
+  if (!e->finalized || !e->group_ready[kGroupVaeDecoder]) return e->fail(MLDHIP_ESTATE, "vae_decode before finalize / vae.* not loaded");
   if (!z_dev || !feats_out_dev) return e->fail(MLDHIP_EINVAL, "null pointer");
   int T = 0;
   if (int rc = validate_lengths(e, lengths_host, B, &T)) return rc;
@@ -627,7 +622,7 @@ int mldhip_vae_encode(mldhip_handle* e, const float* feats_dev, const int32_t* l
                       const float* eps_dev, float* latent_out_dev, float* mu_out_dev, float* logvar_out_dev, void* stream_) {
   if (!e) return MLDHIP_EINVAL;
   DeviceGuard dg(e->device);
-  if (!e->finalized || !e->group_ready[3]) return e->fail(MLDHIP_ESTATE, "vae_encode before finalize / vae.encoder.* not loaded");
+  if (!e->finalized || !e->group_ready[kGroupVaeEncoder]) return e->fail(MLDHIP_ESTATE, "vae_encode before finalize / vae.encoder.* not loaded");
   if (!feats_dev || !mu_out_dev || !logvar_out_dev) return e->fail(MLDHIP_EINVAL, "null pointer");
   if (eps_dev && !latent_out_dev) return e->fail(MLDHIP_EINVAL, "eps given but latent_out is NULL");
   int Tm = 0;
@@ -735,7 +730,7 @@ int mldhip_feats2joints(mldhip_handle* e, const float* feats_dev, int32_t B, int
   if (!e) return MLDHIP_EINVAL;
   DeviceGuard dg(e->device);
   if (is_actor(e) || e->cfg.nfeats < joint_feat_cols(e)) return e->fail(MLDHIP_ESTATE, "feats2joints implements the HumanML3D / KIT-ML layout (recover_from_ric) only (SMPL-based layouts are out of scope)");
-  if (!e->finalized || !e->group_ready[2]) return e->fail(MLDHIP_ESTATE, "feats2joints before finalize / mean,std not loaded");
+  if (!e->finalized || !e->group_ready[kGroupStats]) return e->fail(MLDHIP_ESTATE, "feats2joints before finalize / mean,std not loaded");
   if (!feats_dev || !joints_out_dev) return e->fail(MLDHIP_EINVAL, "null pointer");
   if (B < 1 || T < 1 || T > 512) return e->fail(MLDHIP_EINVAL, "B >= 1 and 1 <= T <= 512 required");
   Ctx c{e, (hipStream_t)stream_};
@@ -754,7 +749,7 @@ int mldhip_profile_kernel(mldhip_handle* e, const char* name, int32_t B, int32_t
   // caller brackets the call with events on the same stream (bench.py does) -- no timing happens here.
   if (!e || !name || !flops_per_launch) return MLDHIP_EINVAL;
   DeviceGuard dg(e->device);
-  if (!e->finalized || !e->group_ready[0] || !e->group_ready[1]) return e->fail(MLDHIP_ESTATE, "profile before finalize");
+  if (!e->finalized || !e->group_ready[kGroupDenoiser] || !e->group_ready[kGroupVaeDecoder]) return e->fail(MLDHIP_ESTATE, "profile before finalize");
   if (B < 1 || B > e->cfg.max_batch || T < 1 || T > e->cfg.max_frames || iters < 1) return e->fail(MLDHIP_EINVAL, "bad B/T/iters");
   CtxUse use(e, (hipStream_t)stream_);
   if (use.rc) return use.rc;
